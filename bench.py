@@ -13,9 +13,16 @@ similarity sets, pass 2, and ONE gather of the final bit-packed masks on rank 0 
 Inputs are resident in HBM (uploaded before the timed region) in the reference's formats: float64 cloud,
 float32 depth, RLE runs.  Scenes shard one per GPU (weak scaling); N = 1 runs the same loop without collectives.
 
-The JSON line also carries `roofline` for the HBM-bound projection sweep (HIP-event timed on the
-launch stream, live) and `cpu_baseline`: the oracle (CPU restatement of the reference) timed on a
-bounded sample of the same scene on this box's host cores.
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline rate, `ms_per_step`, the
+kernels' durations and the host thread's time from the timed loop).  `--full` adds the measurements that take work
+of their own after the timed loop: `roofline` for the HBM-bound projection sweep (HIP-event timed on the launch
+stream, live, and alone on the chip in a sequential loop) and the tile pass, the device span of one scene call,
+`host_inclusive` (the rate from host arrays), the round trip of the last class's gathered results and
+`cpu_baseline`: the oracle (CPU restatement of the reference) timed on a bounded sample of the same scene on the
+host's cores.
+
+`--dump-outputs DIR` writes the final results of the last timed step (one query class) as .npy files, see
+dump_outputs().
 """
 from __future__ import annotations
 
@@ -215,6 +222,9 @@ def bench_cosine(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     ms = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "cosine.npy"), out.cpu().numpy())
     flop = 2.0 * a.shape[0] * b.shape[0] * a.shape[1]
     ref = (a.double() @ b.double().T) / (a.double().norm(dim=1, keepdim=True) * b.double().norm(dim=1, keepdim=True).T)
     err = float((out.double() - ref).abs().max())
@@ -249,6 +259,49 @@ SCENE_VARIANTS = [
     dict(kind="default"), dict(kind="many", cut_masks=False, n_objects=40, distinct_masks=True, dilate=False),
     dict(kind="default"), dict(kind="many", cut_masks=False, n_objects=40, distinct_masks=True, dilate=False),
 ]
+
+
+DUMP_SAMPLE_POINTS = 32768     # point columns of the final masks written by --dump-outputs (fixed, seeded sample)
+DUMP_MASK_BYTES = 48 << 20     # at most this much of sampled masks (fewer columns when a class returns many masks)
+
+
+def dump_outputs(out_dir, final, scene_ids):
+    """--dump-outputs: what a caller of the timed path receives for the last class, scene by scene in class order
+    (FinalResult: bit-packed masks, confidences).  The masks are written on a fixed, seeded sample of point indices
+    (float32 0/1, one row per mask) next to every mask's full point count, so two builds compare output for output:
+      final_masks_per_scene (S,)   masks of each scene (0 for the reference's empty list form)
+      final_conf (R,)              confidence of every mask, float64
+      final_mask_points (R,)       points in every mask over the whole cloud
+      final_masks_sample (R, P)    the masks at the sampled points
+      sample_points (P,)           the sampled point indices"""
+    os.makedirs(out_dir, exist_ok=True)
+    per_scene, conf, points, dense = [], [], [], []
+    n_points = None
+    for sid in scene_ids:
+        f = final.get(sid)
+        if f is None or f.rows is None:
+            per_scene.append(0)
+            continue
+        if n_points is None:
+            n_points = f.n_points
+        assert f.n_points == n_points, "the scenes of one bench run share their point count"
+        per_scene.append(f.rows.shape[0])
+        conf.append(torch.as_tensor(f.conf).double().reshape(-1).cpu())
+        d = _lib.unpack_rows(f.rows, f.n_points)
+        points.append(d.sum(dim=1, dtype=torch.int64).double().cpu())
+        dense.append(d)
+    n_rows = sum(per_scene)
+    n_sample = min(n_points or 0, DUMP_SAMPLE_POINTS, max(1024, DUMP_MASK_BYTES // (4 * max(1, n_rows))))
+    pick = np.sort(np.random.default_rng(0).choice(n_points, size=n_sample, replace=False)) if n_points else np.zeros(0, np.int64)
+    pick_d = torch.from_numpy(pick).to(dense[0].device) if dense else None
+    sample = torch.cat([d[:, pick_d].float().cpu() for d in dense]) if dense else torch.zeros((0, n_sample))
+    arrays = {"final_masks_per_scene": np.asarray(per_scene, dtype=np.float64),
+              "final_conf": torch.cat(conf).numpy() if conf else np.zeros(0),
+              "final_mask_points": torch.cat(points).numpy() if points else np.zeros(0),
+              "final_masks_sample": sample.numpy().astype(np.float32),
+              "sample_points": pick.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def merge_traffic(ds, cfg, dev):
@@ -315,7 +368,12 @@ def main():
                          "refinement (one similarity exchange + one gather at N > 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--shape", default="c2", choices=list(SHAPES) + ["c5"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the rooflines, the scene-call span, the host-inclusive leg, the "
+                         "gathered-results round trip and the CPU baseline (a plain run reports the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the final results of the last timed step to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-stagewise", action="store_true",
                     help="print the stage-wise CPU (oracle) timings of SURVEY 8(d) for --shape and exit")
     ap.add_argument("--cpu-sample-views", type=int, default=100)
@@ -333,7 +391,7 @@ def main():
                     help="scenes per GPU that form one query class: one similarity exchange + one gather per batch")
     ap.add_argument("--include-upload", action="store_true", help="(kept for old command lines: the host-inclusive leg always runs at N = 1)")
     ap.add_argument("--no-host-inclusive", action="store_true",
-                    help="skip the host-inclusive leg (every step takes host arrays -- reference formats, raw 16-bit depth -- "
+                    help="with --full: skip the host-inclusive leg (every step takes host arrays -- reference formats, raw 16-bit depth -- "
                          "through the overlapped ingestion pipeline before the device path; reported as `host_inclusive`)")
     args = ap.parse_args()
     # the host side of the GPU path makes only tiny torch CPU calls; left at the default every one of them opens an OpenMP
@@ -489,76 +547,62 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
-    # the two big kernels alone on the chip: a short strictly sequential loop after the timed region (in the
-    # pipelined loop they share the GPU with the other scene's kernels)
-    seq_timers = KernelTimers(reserve=8 * n_scenes)
-    if not args.no_pipeline:
-        was = args.no_pipeline
-        args.no_pipeline = True
-        run_steps(min(2 * n_scenes, n_timed), seq_timers)
-        args.no_pipeline = was
-        fence()
+    if args.dump_outputs and rank == 0 and last_class.get("batch") is not None:
+        lb = last_class["batch"]                        # the last timed class (the --full loops below replace it)
+        dump_outputs(args.dump_outputs, lb.results(), lb.ids)
 
-    # device span of the one native call per scene (first kernel start -> last kernel end on an otherwise idle GPU,
-    # no host involvement in between): what the chain of ~50 launches costs end to end, per scene variant
-    spans = []
-    for k in range(n_scenes):
-        st = streams[k % depth]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record(st)
-        fr = front(k)
-        e1.record(st)
-        with torch.cuda.stream(st):
-            projection_back(fr, want_groups=False)
-        torch.cuda.synchronize()
-        spans.append(round(e0.elapsed_time(e1), 4))
+    if args.full:
+        # the two big kernels alone on the chip: a short strictly sequential loop after the timed region (in the
+        # pipelined loop they share the GPU with the other scene's kernels)
+        seq_timers = KernelTimers(reserve=8 * n_scenes)
+        if not args.no_pipeline:
+            was = args.no_pipeline
+            args.no_pipeline = True
+            run_steps(min(2 * n_scenes, n_timed), seq_timers)
+            args.no_pipeline = was
+            fence()
 
-    upload_leg = None
-    if world == 1 and not args.no_host_inclusive:
-        from beyond_fixed_forms_amd.ingest import bench_host_inclusive
-        upload_leg = bench_host_inclusive(scenes, cfg, dev, QUERY, sim, steps=min(max(n_timed, 24), 48),
-                                          n_loaders=int(os.environ.get("BFF_BENCH_LOADERS", "4")),
-                                          native_threads=int(os.environ.get("BFF_BENCH_NATIVE_THREADS", "4")))
+        # device span of the one native call per scene (first kernel start -> last kernel end on an otherwise idle GPU,
+        # no host involvement in between): what the chain of ~50 launches costs end to end, per scene variant
+        spans = []
+        for k in range(n_scenes):
+            st = streams[k % depth]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record(st)
+            fr = front(k)
+            e1.record(st)
+            with torch.cuda.stream(st):
+                projection_back(fr, want_groups=False)
+            torch.cuda.synchronize()
+            spans.append(round(e0.elapsed_time(e1), 4))
 
-    # what rank 0 holds after the last class: every rank's final masks, decoded from the gathered buffers only now
-    gathered_check = None
-    if last_class.get("batch") is not None:
-        lb = last_class["batch"]
-        got = lb.results()
-        if rank == 0:
-            own = {sid: f for sid, f in lb.final.items()}
-            same_own = all((got[sid].rows is None and f.rows is None) or
-                           (got[sid].rows is not None and f.rows is not None and torch.equal(got[sid].rows.to(dev), f.rows))
-                           for sid, f in own.items())
-            gathered_check = {"scenes_on_rank0": len(got), "expected": len(lb.ids), "rank0_rows_round_trip": bool(same_own),
-                              "final_masks_total": int(sum(0 if f.rows is None else f.rows.shape[0] for f in got.values()))}
-            assert len(got) == len(lb.ids) and same_own, gathered_check
+        upload_leg = None
+        if world == 1 and not args.no_host_inclusive:
+            from beyond_fixed_forms_amd.ingest import bench_host_inclusive
+            upload_leg = bench_host_inclusive(scenes, cfg, dev, QUERY, sim, steps=min(max(n_timed, 24), 48),
+                                              n_loaders=int(os.environ.get("BFF_BENCH_LOADERS", "4")),
+                                              native_threads=int(os.environ.get("BFF_BENCH_NATIVE_THREADS", "4")))
+
+        # what rank 0 holds after the last class: every rank's final masks, decoded from the gathered buffers only now
+        gathered_check = None
+        if last_class.get("batch") is not None:
+            lb = last_class["batch"]
+            got = lb.results()
+            if rank == 0:
+                own = {sid: f for sid, f in lb.final.items()}
+                same_own = all((got[sid].rows is None and f.rows is None) or
+                               (got[sid].rows is not None and f.rows is not None and torch.equal(got[sid].rows.to(dev), f.rows))
+                               for sid, f in own.items())
+                gathered_check = {"scenes_on_rank0": len(got), "expected": len(lb.ids), "rank0_rows_round_trip": bool(same_own),
+                                  "final_masks_total": int(sum(0 if f.rows is None else f.rows.shape[0] for f in got.values()))}
+                assert len(got) == len(lb.ids) and same_own, gathered_check
 
     if trace_front is not None and rank == 0:
         print("front() ms per call:", trace_front, file=sys.stderr)
     if rank == 0:
         ks = timers.summary()
-        sq = seq_timers.summary() if not args.no_pipeline else ks
         ds = dss[0]
-        n_swept = ds.n_frames
-        pv = ks["project_views"]
-        abytes, zbytes = algorithmic_bytes(ds, n_swept)
-        achieved = abytes / (pv[2] * 1e-3) / 1e9
-        traffic = None
-        tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tfile):
-            with open(tfile) as f:
-                traffic = json.load(f).get(f"project_views_{args.shape}" + ("_u16" if ds.depth_raw is not None else ""))
-        mt = merge_traffic(ds, cfg, dev)
-        comp = compulsory_traffic(ds, dev)
-        t_alone = sq["project_views"][2] * 1e-3
-        comp.update(achieved=comp["bytes"] / t_alone / 1e9, frac=comp["bytes"] / t_alone / 1e9 / HBM_PEAK_GBS,
-                    note="HBM bytes the sweep cannot avoid (each touched 128-B line once, cloud once per frame tile) over its "
-                         "duration alone on the chip; `achieved`/`frac` above use SURVEY 8(d)'s algorithmic bytes, which "
-                         "charge 28 B per (frame, point) even where caches serve them")
-        mc_ms, mc_alone = ks["merge_components"][2], sq["merge_components"][2]
-        l2_bytes = mt["chunk_visits"] * 128 * 64            # every visited chunk: 128 rows x 8 words staged through LDS
         out = {
             "metric": "scenes/sec (2D->3D projection+refinement), 200k pts x 300 views",
             "value": world * n_timed / elapsed, "unit": "scenes/s", "n_gpus": world, "steps": args.steps,
@@ -585,36 +629,58 @@ def main():
                        "pipelining": "none" if args.no_pipeline else
                        f"{depth} HIP streams: the device work of the next {depth - 1} scene(s) overlaps the host half of scene i",
                        "scene_variants": [SCENE_VARIANTS[k % len(SCENE_VARIANTS)]["kind"] for k in range(n_scenes)]},
-            "roofline": {"bound": "hbm", "kernel": "project_views_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic["bytes"] if traffic else None,      # HBM bytes per launch from the PMC counters
-                         "traffic_detail": traffic,
-                         "algorithmic_bytes_per_launch": abytes, "avg_launch_ms": pv[2], "launches": pv[0],
-                         "survey_row_write_bytes_not_credited": zbytes,
-                         "note": "avg_launch_ms is the kernel's duration INSIDE the timed loop, where it shares the chip with the "
-                                 "kernels of the other scenes in flight (HIP events on the dispatch); `alone_on_chip` is the same "
-                                 "kernel in a strictly sequential loop right after it and is what a rocprofv3 kernel trace "
-                                 "shows, because the profiler serialises the streams (profiles/README.md)",
-                         "compulsory": comp,
-                         "alone_on_chip": {"avg_launch_ms": sq["project_views"][2],
-                                           "achieved": abytes / (sq["project_views"][2] * 1e-3) / 1e9,
-                                           "frac": abytes / (sq["project_views"][2] * 1e-3) / 1e9 / HBM_PEAK_GBS}},
-            # second bound: the components' tile pass is AND + popcount over LDS-staged chunks -- not HBM, not MFMA
-            "roofline_merge": {"bound": "l2->lds staging + VALU popcount", "kernel": "merge_components_kernel",
-                               "avg_launch_ms": mc_ms, "alone_on_chip_ms": mc_alone, "launches": ks["merge_components"][0],
-                               "l2_bytes_staged": l2_bytes, "achieved": l2_bytes / (mc_alone * 1e-3) / 1e9,
-                               "peak": 34500.0, "unit": "GB/s (L2, MI355X_MICROARCH.md)",
-                               "frac": l2_bytes / (mc_alone * 1e-3) / 1e9 / 34500.0, **mt},
-            "host_ms": host_ms, "scene_call_device_span_ms": spans,      # wall time of the host thread per SCENE: issuing, the host half, and the part of it spent blocked on the GPU
+            "host_ms": host_ms,                                           # wall time of the host thread per SCENE: issuing, the host half, and the part of it spent blocked on the GPU
             "kernels_ms": {k: round(vv[2], 4) for k, vv in ks.items()},   # the kernels' own durations (events on the dispatch)
-            "result": {"per_scene (stage2_instances, final_masks)": [results.get(k) for k in range(n_scenes)],
-                       "last_class_on_rank0": gathered_check},
+            "result": {"per_scene (stage2_instances, final_masks)": [results.get(k) for k in range(n_scenes)]},
             "setup_s": round(t_setup, 1),
         }
-        if upload_leg is not None:
-            out["host_inclusive"] = upload_leg
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(scenes[0], cfg, bank_encoder(bank.float(), index))
+        if args.full:
+            sq = seq_timers.summary() if not args.no_pipeline else ks
+            n_swept = ds.n_frames
+            pv = ks["project_views"]
+            abytes, zbytes = algorithmic_bytes(ds, n_swept)
+            achieved = abytes / (pv[2] * 1e-3) / 1e9
+            traffic = None
+            tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tfile):
+                with open(tfile) as f:
+                    traffic = json.load(f).get(f"project_views_{args.shape}" + ("_u16" if ds.depth_raw is not None else ""))
+            mt = merge_traffic(ds, cfg, dev)
+            comp = compulsory_traffic(ds, dev)
+            t_alone = sq["project_views"][2] * 1e-3
+            comp.update(achieved=comp["bytes"] / t_alone / 1e9, frac=comp["bytes"] / t_alone / 1e9 / HBM_PEAK_GBS,
+                        note="HBM bytes the sweep cannot avoid (each touched 128-B line once, cloud once per frame tile) over its "
+                             "duration alone on the chip; `achieved`/`frac` above use SURVEY 8(d)'s algorithmic bytes, which "
+                             "charge 28 B per (frame, point) even where caches serve them")
+            mc_ms, mc_alone = ks["merge_components"][2], sq["merge_components"][2]
+            l2_bytes = mt["chunk_visits"] * 128 * 64            # every visited chunk: 128 rows x 8 words staged through LDS
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": "project_views_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "traffic": traffic["bytes"] if traffic else None,      # HBM bytes per launch from the PMC counters
+                             "traffic_detail": traffic,
+                             "algorithmic_bytes_per_launch": abytes, "avg_launch_ms": pv[2], "launches": pv[0],
+                             "survey_row_write_bytes_not_credited": zbytes,
+                             "note": "avg_launch_ms is the kernel's duration INSIDE the timed loop, where it shares the chip with the "
+                                     "kernels of the other scenes in flight (HIP events on the dispatch); `alone_on_chip` is the same "
+                                     "kernel in a strictly sequential loop right after it and is what a rocprofv3 kernel trace "
+                                     "shows, because the profiler serialises the streams (profiles/README.md)",
+                             "compulsory": comp,
+                             "alone_on_chip": {"avg_launch_ms": sq["project_views"][2],
+                                               "achieved": abytes / (sq["project_views"][2] * 1e-3) / 1e9,
+                                               "frac": abytes / (sq["project_views"][2] * 1e-3) / 1e9 / HBM_PEAK_GBS}},
+                # second bound: the components' tile pass is AND + popcount over LDS-staged chunks -- not HBM, not MFMA
+                "roofline_merge": {"bound": "l2->lds staging + VALU popcount", "kernel": "merge_components_kernel",
+                                   "avg_launch_ms": mc_ms, "alone_on_chip_ms": mc_alone, "launches": ks["merge_components"][0],
+                                   "l2_bytes_staged": l2_bytes, "achieved": l2_bytes / (mc_alone * 1e-3) / 1e9,
+                                   "peak": 34500.0, "unit": "GB/s (L2, MI355X_MICROARCH.md)",
+                                   "frac": l2_bytes / (mc_alone * 1e-3) / 1e9 / 34500.0, **mt},
+                "scene_call_device_span_ms": spans})
+            out["result"]["last_class_on_rank0"] = gathered_check
+            if upload_leg is not None:
+                out["host_inclusive"] = upload_leg
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(scenes[0], cfg, bank_encoder(bank.float(), index))
         print(json.dumps(out))
     if world > 1 or forced:
         dist.barrier()
