@@ -27,6 +27,7 @@ SIGNATURES = {
     "bff_depth_tile_u16": [_P, _I, _I, _I, _P, _I, _P],
     "bff_project_views_u16": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P],
     "bff_point_tile_bounds": [_P, _L, _L, _P, _P],
+    "bff_count_viewed": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _I, _P, _P, _P],
     "bff_popcount_rows": [_P, _P, _I, _L, _P, _P],
     "bff_cross_popcount": [_P, _P, _I, _P, _P, _I, _L, _P, _P],
     "bff_row_stats": [_P, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P],
@@ -61,6 +62,7 @@ SIGNATURES = {
     "bff_resolve_overlaps_dev": [_P, _I, _L, _P, _P, _P, _P, _P, _P],
     "bff_clear_flagged_chunks_unless": [_P, _I, _L, _P, _P, _P],
     "bff_scene_project": [_P, _P, _P, _P],
+    "bff_scene_project_viewed": [_P, _P, _P, _P, _P],
     "bff_diag_gather": [_P, _L, _L, _P, _P],
     "bff_diag_sweep_lines": [_P, _L, _L, _P, _P, _I, _P, _P, _I, _I, _D, _P, _I, _P, _P, _P, _L, _P, _P],
     "bff_diag_sweep_lines_u16": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _P, _I, _P, _P, _P, _L, _P, _P],
@@ -279,6 +281,26 @@ def project_views(xyz_soa, n_points, inv_pose, cam_intr, depth, depth_index, hei
          _ptr(frame_nmask, i32), _ptr(frame_flags, i32), _ptr(rows, i64),
          0 if rows is None else rows.shape[0], nw, _ptr(chunk_mask, i64), _ptr(masked_count, i32),
          _ptr(viewed_count, i32), _ptr(tile_bounds, f64))
+
+
+def count_viewed(xyz_soa, n_points, inv_pose, cam_intr, depth, depth_index, height, width, depth_thresh, viewed_count,
+                 tile_bounds=None, depth_size=None, frames_per_block=None):
+    """viewed_count (int32 [n_points], zeroed by the caller) += visibility of every point in every frame of `inv_pose`
+    (bff_count_viewed): the detection-ratio sweep of project_views without masks.  `depth` / `depth_size` as project_views.
+    frames_per_block: frame tile of a block (None: BFF_VIEWED_TILE, else the library's choice)."""
+    k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
+    if depth.dtype == torch.int16 or depth_size is not None:
+        hs, ws = (depth_size if depth_size is not None else depth.shape[1:3])
+        layout = 0 if depth_size is None else (2 if depth.dtype == f32 else 1)
+    else:
+        hs, ws, layout = 0, 0, -1
+        if depth.dtype != f32:
+            raise TypeError(f"expected float32 depth images, got {depth.dtype}")
+    if frames_per_block is None:
+        frames_per_block = int(os.environ.get("BFF_VIEWED_TILE", "0"))
+    call("bff_count_viewed", _ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(inv_pose, f64), ctypes.cast(k, c_void_p),
+         inv_pose.shape[0], _ptr(depth), int(hs), int(ws), layout, _ptr(depth_index, i32), height, width,
+         float(depth_thresh), int(frames_per_block), _ptr(viewed_count, i32), _ptr(tile_bounds, f64))
 
 
 def tile_depth(raw, metres=True):

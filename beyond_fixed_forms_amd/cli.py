@@ -96,16 +96,30 @@ def _coll_device(device):
     return device if dist.get_backend() == "nccl" else "cpu"
 
 
+def _projection_parser():
+    """P:314-318, with --cls repeatable: several query classes in one run (each scene read and uploaded once)."""
+    p = argparse.ArgumentParser(description="Beyond-Fixed-Forms 2D->3D projection (MI355X)")
+    p.add_argument("--config", type=str, required=True, help="Config")
+    p.add_argument("--cls", type=str, required=True, action="append",
+                   help="Class; give it more than once to project several classes in one run")
+    return p
+
+
 def projection_main(argv=None):
-    """python tools/projection_2d_to_3d.py --config configs/config.yaml --cls "<class>"   (P:336-634)"""
-    args = _parser("Beyond-Fixed-Forms 2D->3D projection (MI355X)").parse_args(argv)
+    """python tools/projection_2d_to_3d.py --config configs/config.yaml --cls "<class>" [--cls "<class>" ...]
+    (P:336-634).  One --cls: the reference's run.  Several: every class's files, checkpoint and log lines exactly as
+    its own run writes them, each scene read, uploaded and viewed-counted once for all of its classes."""
+    args = _projection_parser().parse_args(argv)
     rc = launch_ranks(argv)
     if rc is not None:
         return rc
     cfg = load_config(args.config)
     _lib.load()
     _host_threads()
-    cls = args.cls
+    classes = list(dict.fromkeys(args.cls))
+    if len(classes) > 1:
+        return _projection_classes(cfg, classes)
+    cls = classes[0]
     from .distributed import shard_scenes
     from .pipeline import project_stream
     rank, ws, device = init_ranks()
@@ -150,6 +164,64 @@ def projection_main(argv=None):
             for i in torch.nonzero(flags.cpu()).view(-1).tolist():
                 ckpt[scene_ids[i]] = True
             write_scene_checkpoint("projection_2d_to_3d", cls, ckpt)
+        _finish_ranks()
+    return 0
+
+
+def class_scenes(mask_2d_dir, classes):
+    """Scenes of a multi-class run: each class's own listing mask_2d/<cls>/*_00.pth (P:363), their union in sorted
+    order, and for every scene the classes that list it, in the given order.  -> (scene ids, [classes per scene])."""
+    lists = {c: {s[:-4] for s in os.listdir(os.path.join(mask_2d_dir, c)) if s.endswith("_00.pth")} for c in classes}
+    scene_ids = sorted(set().union(*lists.values()))
+    return scene_ids, [[c for c in classes if sid in lists[c]] for sid in scene_ids]
+
+
+def _projection_classes(cfg, classes):
+    """The projection stage for several classes: scenes = the union of the classes' mask_2d listings (P:363) in sorted
+    order, each projected for the classes that list it, in command-line order (pipeline.project_classes_stream)."""
+    from .distributed import shard_scenes
+    from .io import load_scene_classes
+    from .pipeline import project_classes_stream
+    rank, ws, device = init_ranks()
+    ckpts = {c: read_scene_checkpoint("projection_2d_to_3d", c) for c in classes}
+    scene_ids, per_scene = class_scenes(cfg.mask_2d_dir, classes)
+    weights = None
+    if ws > 1:
+        weights = [os.path.getsize(p) if os.path.exists(p) else 0
+                   for p in (os.path.join(cfg.scene_npy_dir, f"{s}.npy") for s in scene_ids)]
+    mine = shard_scenes(scene_ids, rank, ws, weights)
+    on_dev = os.environ.get("BFF_DEPTH_ON_DEVICE") == "1"
+    items = []
+    for i in mine:
+        items.append((functools.partial(load_scene_classes, cfg, per_scene[i], scene_ids[i], depth_on_device=on_dev),
+                       per_scene[i]))
+    done = []                                   # (class index, scene index) of the non-empty results
+
+    def consume(k, cls, _st1, res):
+        scene_id = scene_ids[mine[k]]
+        print("Working on", scene_id, "class", cls)
+        if not res.debug.get("empty_form", False):
+            done.append((classes.index(cls), mine[k]))
+            if ws == 1:
+                ckpts[cls][scene_id] = True                                               # P:580-581
+                write_scene_checkpoint("projection_2d_to_3d", cls, ckpts[cls])
+        out = res.to_rle_dict() if os.environ.get("BFF_SAVE_RLE") == "1" and not res.debug.get("empty_form") else res.to_dict()
+        save_result(out, cfg.mask_3d_dir, cls, scene_id)                                    # P:630-634
+
+    project_classes_stream(items, cfg, device, consume, n_loaders=int(os.environ.get("BFF_LOADERS", "2")))
+    if ws > 1:
+        # one reduction of the (class, scene) completion flags; rank 0 alone writes every class's checkpoint
+        flags = torch.zeros((len(classes), max(len(scene_ids), 1)), dtype=torch.int32, device=_coll_device(device))
+        if done:
+            idx = torch.tensor(done, dtype=torch.long)
+            flags[idx[:, 0], idx[:, 1]] = 1
+        dist.reduce(flags, dst=0, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            got = flags.cpu()
+            for ci, c in enumerate(classes):
+                for i in torch.nonzero(got[ci]).view(-1).tolist():
+                    ckpts[c][scene_ids[i]] = True
+                write_scene_checkpoint("projection_2d_to_3d", c, ckpts[c])
         _finish_ranks()
     return 0
 

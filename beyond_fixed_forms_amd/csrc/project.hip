@@ -464,6 +464,146 @@ __global__ void sweep_lines_kernel(const double *__restrict__ xyz, int64_t n_poi
     atomicOr(mask_lines + (int64_t)f * line_words + (ml >> 5), 1u << (ml & 31));
 }
 
+// The detection-ratio sweep alone (P:538-567): viewed_count[n] += visible(n, f) for every frame of the list.  Per (point,
+// frame) exactly the arithmetic of project_views_kernel -- the same fma chains, rint, bounds on the doubles, RawDepth taps
+// and bilinear order, depth test -- so the counts are the ones the fused sweep adds under frame flag bit 0.  Same block
+// shape (1024 points, 4 per thread in registers, frames tiled over blockIdx.y); without masks there are no gathers of
+// mask words, no ballot transposition and no row stores, so a block takes a longer frame tile (fewer atomics per point):
+// the tile is culled against tile_bounds in groups of 8 frames, the fused sweep's exact test.
+constexpr int kCullGroup = 8;                    // frames one culling pass decides (lane = 8 frame + corner)
+
+template <bool kRaw>
+__global__ __launch_bounds__(kBlock) void viewed_count_kernel(
+    const double *__restrict__ xyz, int64_t n_points, int64_t n_pad,
+    const double *__restrict__ inv_pose, Intrinsics K, int n_frames, int frames_per_block,
+    const void *__restrict__ depth, RawDepth raw, const int32_t *__restrict__ depth_index, int H, int W, double thresh,
+    int32_t *__restrict__ viewed_count, const double *__restrict__ tile_bounds)
+{
+    extern __shared__ uint32_t s_taps[];
+    if (kRaw) {
+        const int n_vec = (3 * raw.n_taps + 3) / 4;
+        const uint4 *src = reinterpret_cast<const uint4 *>(raw.taps);
+        uint4 *dst = reinterpret_cast<uint4 *>(s_taps);
+        for (int i = (int)threadIdx.x; i < n_vec; i += kBlock) dst[i] = src[i];
+        __syncthreads();
+    }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t word0 = (int64_t)blockIdx.x * kWordsPerBlock + (int64_t)wave * kPPT;
+    const int f0 = blockIdx.y * frames_per_block;
+    const int f1 = min(n_frames, f0 + frames_per_block);
+    const int64_t hw = (int64_t)H * W;
+    const double dW = (double)W, dH = (double)H;
+
+    double px[kPPT], py[kPPT], pz[kPPT];
+    bool valid[kPPT];
+    int vcount[kPPT];
+#pragma unroll
+    for (int j = 0; j < kPPT; ++j) {
+        const int64_t n = (word0 + j) * kWave + lane;
+        valid[j] = n < n_points;
+        const int64_t m = valid[j] ? n : 0;
+        px[j] = xyz[m];
+        py[j] = xyz[n_pad + m];
+        pz[j] = xyz[2 * n_pad + m];
+        vcount[j] = 0;
+    }
+
+    for (int g0 = f0; g0 < f1; g0 += kCullGroup) {
+        const int g1 = min(f1, g0 + kCullGroup);
+        // frustum culling of the wave's 256 points against the <= 8 frames [g0, g1): project_views_kernel's test
+        uint64_t culled = 0;
+        if (tile_bounds && word0 * kWave < n_points) {     // wave-uniform; the table has one box per tile that holds points
+            const double *bb = tile_bounds + 6 * (word0 / kPPT);
+            const int corner = lane & 7, fk = lane >> 3;
+            const double bx = (corner & 1) ? bb[3] : bb[0], by = (corner & 2) ? bb[4] : bb[1], bz = (corner & 4) ? bb[5] : bb[2];
+            double l1 = 0.0, l2 = 0.0, l3 = 0.0, l4 = 0.0;
+            if (g0 + fk < g1) {
+                const double *P = inv_pose + 16 * (int64_t)(g0 + fk);
+                const double cx = fma(P[2], bz, fma(P[1], by, P[0] * bx)) + P[3];
+                const double cy = fma(P[6], bz, fma(P[5], by, P[4] * bx)) + P[7];
+                const double cz = fma(P[10], bz, fma(P[9], by, P[8] * bx)) + P[11];
+                const double p0 = fma(K.k[2], cz, fma(K.k[1], cy, K.k[0] * cx));
+                const double p1 = fma(K.k[5], cz, fma(K.k[4], cy, K.k[3] * cx));
+                constexpr double m = 0.01;
+                l1 = fma(0.5 + m, cz, p0);
+                l2 = fma(dW - 0.5 + m, cz, -p0);
+                l3 = fma(0.5 + m, cz, p1);
+                l4 = fma(dH - 0.5 + m, cz, -p1);
+            }
+            constexpr double delta = 1e-6;
+            auto all8 = [](uint64_t b) {
+                b &= b >> 1; b &= b >> 2; b &= b >> 4;
+                return b & 0x0101010101010101ull;
+            };
+            const uint64_t neg = all8(__ballot(l1 < -delta)) | all8(__ballot(l2 < -delta)) |
+                                 all8(__ballot(l3 < -delta)) | all8(__ballot(l4 < -delta));
+            const uint64_t pos = all8(__ballot(l1 > delta)) | all8(__ballot(l2 > delta)) |
+                                 all8(__ballot(l3 > delta)) | all8(__ballot(l4 > delta));
+            culled = neg & pos;
+        }
+        for (int f = g0; f < g1; ++f) {
+            if ((culled >> (8 * (f - g0))) & 1) continue;      // wave-uniform
+            const double *P = inv_pose + 16 * (int64_t)f;
+            const float *dimg = kRaw ? nullptr : reinterpret_cast<const float *>(depth) + (int64_t)depth_index[f] * hw;
+            const char *rimg = kRaw ? reinterpret_cast<const char *>(depth) +
+                                      (int64_t)depth_index[f] * raw.frame_stride * (raw.texel_f32 ? 4 : 2) : nullptr;
+            int pix[kPPT], pu[kPPT];
+            double cz[kPPT];
+#pragma unroll
+            for (int j = 0; j < kPPT; ++j) {
+                const double cx = fma(P[3], 1.0, fma(P[2], pz[j], fma(P[1], py[j], fma(P[0], px[j], 0.0))));
+                const double cy = fma(P[7], 1.0, fma(P[6], pz[j], fma(P[5], py[j], fma(P[4], px[j], 0.0))));
+                cz[j] = fma(P[11], 1.0, fma(P[10], pz[j], fma(P[9], py[j], fma(P[8], px[j], 0.0))));
+                const double p0 = fma(K.k[2], cz[j], fma(K.k[1], cy, fma(K.k[0], cx, 0.0)));
+                const double p1 = fma(K.k[5], cz[j], fma(K.k[4], cy, fma(K.k[3], cx, 0.0)));
+                const double u = rint(p0 / cz[j]);
+                const double v = rint(p1 / cz[j]);
+                const bool inb = valid[j] && (u >= 0.0) && (u < dW) && (v >= 0.0) && (v < dH);   // NaN fails
+                pix[j] = inb ? (int)v * W + (int)u : -1;
+                pu[j] = inb ? (int)u | ((int)v << 16) : 0;
+            }
+            float dval[kPPT];
+            float t00[kPPT], t01[kPPT], t10[kPPT], t11[kPPT];
+            float ta[kPPT], tb[kPPT];
+#pragma unroll
+            for (int j = 0; j < kPPT; ++j) {
+                dval[j] = 0.0f;
+                if (kRaw) {
+                    t00[j] = t01[j] = t10[j] = t11[j] = 0.0f;
+                    ta[j] = tb[j] = 0.0f;
+                }
+                if (pix[j] >= 0) {
+                    if (kRaw) {
+                        const int ux = pu[j] & 0xffff, vy = pu[j] >> 16;
+                        const uint32_t *tx = s_taps + 3 * ux, *ty = s_taps + 3 * (W + vy);
+                        const uint32_t c0 = tx[0], c1 = tx[1], r0 = ty[0], r1 = ty[1];
+                        ta[j] = __uint_as_float(tx[2]);
+                        tb[j] = __uint_as_float(ty[2]);
+                        t00[j] = sensor_texel(rimg, r0 + c0, raw); t01[j] = sensor_texel(rimg, r0 + c1, raw);
+                        t10[j] = sensor_texel(rimg, r1 + c0, raw); t11[j] = sensor_texel(rimg, r1 + c1, raw);
+                    } else {
+                        dval[j] = dimg[pix[j]];
+                    }
+                }
+            }
+            if (kRaw) {
+#pragma unroll
+                for (int j = 0; j < kPPT; ++j)
+                    if (pix[j] >= 0)
+                        dval[j] = bilinear_depth(t00[j], t01[j], t10[j], t11[j], ta[j], tb[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < kPPT; ++j)
+                vcount[j] += ((pix[j] >= 0) && (dval[j] != 0.0f) && (fabs(cz[j] - (double)dval[j]) < thresh)) ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kPPT; ++j) {
+        const int64_t n = (word0 + j) * kWave + lane;
+        if (valid[j] && vcount[j]) atomicAdd(viewed_count + n, vcount[j]);
+    }
+}
+
 // Bounding boxes of the sweep's point tiles (one wave of project_views_kernel = kPPT words = 256 consecutive points
 // of the spatially sorted cloud): bounds[t] = (xmin, ymin, zmin, xmax, ymax, zmax).  NaN coordinates are ignored
 // (such a point is never in bounds), an empty tile gives (+inf, -inf) and is never culled.
@@ -1041,6 +1181,48 @@ extern "C" int bff_project_views_u16(const double *xyz, int64_t n_points, int64_
                                 width, depth_thresh, maskbits, labels, segmap, word_bits, frame_mask, frame_rowbase,
                                 frame_nmask, frame_flags, rows, n_rows, nw, chunk_mask, masked_count, viewed_count,
                                 tile_bounds, stream);
+}
+
+extern "C" int bff_count_viewed(const double *xyz, int64_t n_points, int64_t n_pad, const double *inv_pose,
+                                const double *cam_intr_host, int32_t n_frames, const void *depth, int32_t depth_h,
+                                int32_t depth_w, int32_t depth_layout, const int32_t *depth_index, int32_t height,
+                                int32_t width, double depth_thresh, int32_t frames_per_block, int32_t *viewed_count,
+                                const double *tile_bounds, void *stream)
+{
+    BFF_REQUIRE(n_points >= 0 && n_pad >= n_points && n_frames >= 0 && frames_per_block >= 0, "bff_count_viewed: bad sizes");
+    BFF_REQUIRE(height > 0 && width > 0, "bff_count_viewed: bad image size");
+    BFF_LIMIT((int64_t)height * width < (1ll << 31), "bff_count_viewed: image larger than 2^31 pixels");
+    BFF_REQUIRE(depth_layout >= -1 && depth_layout <= 2, "bff_count_viewed: depth_layout must be -1, 0, 1 or 2");
+    if (n_points == 0 || n_frames == 0) return BFF_OK;
+    BFF_REQUIRE(xyz && inv_pose && cam_intr_host && depth && depth_index && viewed_count, "bff_count_viewed: null pointer");
+    hipStream_t st = as_stream(stream);
+    RawDepth rd{};
+    size_t taps_bytes = 0;
+    if (depth_layout >= 0) {
+        BFF_LIMIT(height < (1 << 15) && width < (1 << 16), "bff_count_viewed: image too large");
+        const int rc = raw_depth_params(depth_h, depth_w, height, width, depth_layout, st, &rd);
+        if (rc != BFF_OK) return rc;
+        taps_bytes = sizeof(uint32_t) * ((3 * (size_t)rd.n_taps + 3) / 4 * 4);
+        BFF_LIMIT(taps_bytes <= 48 * 1024, "bff_count_viewed: the resize's tap table exceeds 48 KB of LDS: resize in a "
+                  "separate pass (bff_depth_from_u16)");
+    }
+    Intrinsics K;
+    for (int i = 0; i < 9; ++i) K.k[i] = cam_intr_host[i];
+    const int64_t gx = ceil_div(n_points, kPtsPerBlock);
+    int fpb = frames_per_block;
+    if (fpb == 0) {        // >= ~4096 blocks in flight, tiles of up to 8 frames (c2, 300 frames: 16 and 32 are slower)
+        fpb = (int)((int64_t)n_frames * gx / 4096);
+        fpb = fpb < 1 ? 1 : (fpb > 8 ? 8 : fpb);
+    }
+    BFF_LIMIT(ceil_div(n_frames, fpb) <= 65535, "bff_count_viewed: too many frame tiles");
+    dim3 grid((unsigned)gx, (unsigned)ceil_div(n_frames, fpb));
+    if (depth_layout >= 0)
+        viewed_count_kernel<true><<<grid, kBlock, (unsigned)taps_bytes, st>>>(xyz, n_points, n_pad, inv_pose, K, n_frames, fpb,
+            depth, rd, depth_index, height, width, depth_thresh, viewed_count, tile_bounds);
+    else
+        viewed_count_kernel<false><<<grid, kBlock, 0, st>>>(xyz, n_points, n_pad, inv_pose, K, n_frames, fpb,
+            depth, rd, depth_index, height, width, depth_thresh, viewed_count, tile_bounds);
+    return launched("bff_count_viewed");
 }
 
 extern "C" int bff_point_tile_bounds(const double *xyz, int64_t n_points, int64_t n_pad, double *bounds, void *stream)

@@ -54,6 +54,12 @@ extern "C" int32_t bff_scene_struct_bytes(int32_t which)
 extern "C" int bff_scene_project(const bff_scene *sc, const bff_scene_params *pr, const bff_scene_workspace *ws,
                                  void *stream)
 {
+    return bff_scene_project_viewed(sc, pr, ws, nullptr, stream);
+}
+
+extern "C" int bff_scene_project_viewed(const bff_scene *sc, const bff_scene_params *pr, const bff_scene_workspace *ws,
+                                        const int32_t *viewed_in, void *stream)
+{
     BFF_REQUIRE(sc && pr && ws, "bff_scene_project: null struct");
     BFF_REQUIRE(sc->n_points > 0 && sc->n_rows > 0 && sc->n_mviews > 0 && sc->n_frames > 0,
                 "bff_scene_project: empty scenes take the general path");
@@ -113,17 +119,21 @@ extern "C" int bff_scene_project(const bff_scene *sc, const bff_scene_params *pr
                               sc->word_bits, ws->labels, ws->maskbits, ws->segmap, hv));
     // a2-a8 (+a15): the fused sweep.  ws->rows is all zero on entry (and again on exit, see below)
     const bool ratio = pr->filter_mode == 2;
+    // the detection ratio's denominator: counted by this sweep (frames with flag bit 0), or given by the caller
+    // (bff_count_viewed over the scene's viewed frames, shared by the classes of the scene)
+    int32_t *const sweep_viewed = (ratio && !viewed_in) ? ws->viewed : nullptr;
+    const int32_t *const viewed = ratio ? (viewed_in ? viewed_in : ws->viewed) : nullptr;
     if (sc->depth_raw)          // depth as the PNGs store it: /1000 + bilinear resize per point inside the sweep
         BFF_TRY(bff_project_views_u16(sc->xyz, n, sc->n_pad, sc->inv_pose, sc->cam_intr, sc->n_frames, sc->depth_raw,
                                       sc->depth_h, sc->depth_w, sc->depth_tiled, sc->depth_index, sc->height, sc->width, pr->depth_thresh,
                                       ws->maskbits, ws->labels, ws->segmap, sc->word_bits, sc->frame_mask, sc->frame_rowbase,
                                       sc->frame_nmask, sc->frame_flags, ws->rows, n_rows, nw, ws->chunk_mask, ws->masked,
-                                      ratio ? ws->viewed : nullptr, sc->tile_bounds, hv));
+                                      sweep_viewed, sc->tile_bounds, hv));
     else
         BFF_TRY(bff_project_views(sc->xyz, n, sc->n_pad, sc->inv_pose, sc->cam_intr, sc->n_frames, sc->depth, sc->depth_index,
                                   sc->height, sc->width, pr->depth_thresh, ws->maskbits, ws->labels, ws->segmap, sc->word_bits,
                                   sc->frame_mask, sc->frame_rowbase, sc->frame_nmask, sc->frame_flags, ws->rows, n_rows, nw,
-                                  ws->chunk_mask, ws->masked, ratio ? ws->viewed : nullptr, sc->tile_bounds, hv));
+                                  ws->chunk_mask, ws->masked, sweep_viewed, sc->tile_bounds, hv));
     if (two) BFF_TRY(hand_over(ws->events[1], hv, stream));
     // a14 / a15: point filter, threshold stays on the device (header words 2, 3 = n_unique, thr).  Nothing before the
     // overlap resolution reads `keep`: with an aux stream the chain forks here and joins there.
@@ -136,17 +146,17 @@ extern "C" int bff_scene_project(const bff_scene *sc, const bff_scene_params *pr
     }
     if (pr->filter_mode != 0) {
         if (pr->filter_sort) {          // the general formulation: sort all n values (more distinct ones than the set holds)
-            BFF_TRY(bff_point_values(ws->masked, ratio ? ws->viewed : nullptr, n, ws->vals, stream));
+            BFF_TRY(bff_point_values(ws->masked, viewed, n, ws->vals, stream));
             size_t tb = ws->sort_temp_bytes;
             BFF_TRY(bff_sort_f32(ws->vals, ws->vals_sorted, n, ws->sort_temp, &tb, stream));
             BFF_TRY(bff_select_unique_rank(ws->vals_sorted, n, pr->filter_fraction, ws->sel_scratch,
                                            reinterpret_cast<float *>(hdr + BFF_HDR_THR), hdr + BFF_HDR_NUNIQUE, stream));
         } else {                        // the statistic is a function of (masked, viewed): distinct values, no sort
-            BFF_TRY(bff_point_threshold_pairs(ws->masked, ratio ? ws->viewed : nullptr, n, pr->filter_fraction,
+            BFF_TRY(bff_point_threshold_pairs(ws->masked, viewed, n, pr->filter_fraction,
                                               ws->pair_scratch, reinterpret_cast<float *>(hdr + BFF_HDR_THR),
                                               hdr + BFF_HDR_NUNIQUE, hdr + BFF_HDR_OVERFLOW, stream));
         }
-        BFF_TRY(bff_ratio_keep(ws->masked, ratio ? ws->viewed : nullptr, n, 0.0f,
+        BFF_TRY(bff_ratio_keep(ws->masked, viewed, n, 0.0f,
                                reinterpret_cast<const float *>(hdr + BFF_HDR_THR), 1, nw, ws->keep, stream));
     } else {
         BFF_TRY(bff_ratio_keep(ws->masked, nullptr, n, 0.0f, nullptr, 0, nw, ws->keep, stream));

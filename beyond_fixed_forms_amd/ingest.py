@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .scene import DeviceScene, keep_raw_depth, prepare_scene, tile_raw_depth, viewed_frame_ids
+from .scene import (DeviceScene, SceneGeometry, class_frame_table, class_word_bits, count_geometry_viewed, frame_union,
+                    keep_raw_depth, prepare_class, prepare_geometry, prepare_scene, tile_raw_depth, viewed_frame_ids)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libbff_host.so")
@@ -205,70 +206,14 @@ def prepare_scene_fast(scene, cfg, device="cuda", with_viewed=True, staging: Sta
 
     lap("run-table upload + pose inverses")
     # ---- depth: frames packed into pinned staging by native threads, ONE asynchronous copy
-    raw_keep = raw_size = None
-    raw_depth = getattr(scene, "depths_raw", None)
-    src = raw_depth if raw_depth is not None else scene.depths
-    frames = [src[f] for f in depth_ids]
-    if frames:
-        f0 = frames[0]
-        want_dtype = np.uint16 if raw_depth is not None else np.float32
-        if any(getattr(f, "dtype", None) != want_dtype or f.shape != f0.shape or not f.flags.c_contiguous for f in frames) or \
-                (raw_depth is None and f0.shape != (h, w)):
-            return prepare_scene(scene, cfg, device=device, with_viewed=with_viewed)   # mixed sizes / dtypes: slow path
-        each = f0.nbytes
-        # the frames may already lie, in upload order, in page-locked memory: a decoder that wrote them there
-        # (io.load_scene(staging=...) -> this loader's "depth" buffer) or the caller's own pinned block
-        staged = getattr(scene, "depth_staged", None) if raw_depth is not None else None
-        flat = None
-        if staged is not None and list(staged[1]) == depth_ids:
-            held = staged[0].buf.get("depth") if isinstance(staged[0], Staging) else staged[0]
-            if torch.is_tensor(held) and held.is_pinned() and held.numel() * held.element_size() >= each * len(frames):
-                flat = held.view(-1).view(torch.uint8)[:each * len(frames)]
-        if flat is None:
-            stage = staging.get("depth", each * len(frames))
-            if host_lib().bff_host_pack_frames(frames, stage.data_ptr(), each, n_threads) != len(frames):
-                return prepare_scene(scene, cfg, device=device, with_viewed=with_viewed)
-            flat = stage[:each * len(frames)]
-        if raw_depth is not None:
-            from .io import bilinear_taps
-            hs, ws_ = f0.shape
-            raw_dev = flat.view(torch.int16).view(len(frames), hs, ws_).to(dev, non_blocking=True)
-            if keep_raw_depth(n, h, w):              # resident at the sensor's resolution: the sweep resizes per point
-                depth_dev, raw_keep = None, raw_dev
-                if tile_raw_depth():
-                    raw_keep, raw_size = _lib.tile_depth(raw_dev, metres=tile_raw_depth() == "f32"), (hs, ws_)
-            else:
-                taps = None
-                if (hs, ws_) != (h, w):
-                    taps = _taps_cache(hs, ws_, h, w, dev)
-                depth_dev = _lib.depth_from_u16(raw_dev, h, w, taps)
-        else:
-            depth_dev = flat.view(torch.float32).view(len(frames), h * w).to(dev, non_blocking=True)
-    else:
-        depth_dev = torch.zeros((0, h * w), dtype=torch.float32, device=dev)
+    got = _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads)
+    if got is None:
+        return prepare_scene(scene, cfg, device=device, with_viewed=with_viewed)       # mixed sizes / dtypes: slow path
+    depth_dev, raw_keep, raw_size = got
 
     lap("depth (pack / enqueue / tile)")
     # ---- cloud: upload as stored, sort + lay out on the device
-    pstage = staging.get("points", pts.nbytes)
-    np.copyto(pstage.numpy()[:pts.nbytes].view(np.float64).reshape(n, stride), pts)
-    pts_dev = pstage[:pts.nbytes].view(torch.float64).view(n, stride).to(dev, non_blocking=True)
-    xyz = torch.empty((3, n_pad), dtype=torch.float64, device=dev)
-    unsort = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    sort = n > 1
-    perm = None
-    if n:
-        perm = torch.empty(n, dtype=torch.int32, device=dev)
-        codes = torch.empty(2 * n, dtype=torch.int32, device=dev)
-        box = torch.empty(6, dtype=torch.float64, device=dev)
-        need = ctypes.c_size_t(0)
-        _lib.call("bff_cloud_layout", None, n, stride, n_pad, 1, None, None, None, None, None, None, ctypes.byref(need))
-        temp = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev)
-        nbytes = ctypes.c_size_t(temp.numel())
-        _lib.call("bff_cloud_layout", _lib._ptr(pts_dev), n, stride, n_pad, 1 if sort else 0, _lib._ptr(xyz), _lib._ptr(unsort),
-                  _lib._ptr(perm), _lib._ptr(codes), _lib._ptr(box), _lib._ptr(temp), ctypes.byref(nbytes))
-    else:
-        xyz.zero_()
-    bounds = _lib.point_tile_bounds(xyz, n) if n else None
+    xyz, unsort, perm, sort, bounds = _cloud_to_device(pts, n, stride, n_pad, dev, staging)
 
     lap("cloud (copy to pinned, enqueue, layout)")
     # ---- small tables: one pinned block, one copy
@@ -339,6 +284,181 @@ def prepare_scene_fast(scene, cfg, device="cuda", with_viewed=True, staging: Sta
         labels=labels, label_id=label_d, n_label_ids=max(1, len(ids)), stage1=getattr(scene, "stage1", None),
         unsort=unsort[:n] if sort else None, perm=perm if sort else None, depth_raw=raw_keep, depth_size=raw_size)
 
+
+def _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads):
+    """The frames `depth_ids` of a scene on the device, in that order (prepare_scene_fast's layout rules): packed into
+    pinned staging by native threads and uploaded as ONE asynchronous copy.  -> (depth, depth_raw, depth_size), or None
+    when the frames are of mixed sizes / dtypes (the caller takes the exact slow path)."""
+    raw_keep = raw_size = None
+    raw_depth = getattr(scene, "depths_raw", None)
+    src = raw_depth if raw_depth is not None else scene.depths
+    frames = [src[f] for f in depth_ids]
+    if frames:
+        f0 = frames[0]
+        want_dtype = np.uint16 if raw_depth is not None else np.float32
+        if any(getattr(f, "dtype", None) != want_dtype or f.shape != f0.shape or not f.flags.c_contiguous for f in frames) or \
+                (raw_depth is None and f0.shape != (h, w)):
+            return None
+        each = f0.nbytes
+        # the frames may already lie, in upload order, in page-locked memory: a decoder that wrote them there
+        # (io.load_scene(staging=...) -> this loader's "depth" buffer) or the caller's own pinned block
+        staged = getattr(scene, "depth_staged", None) if raw_depth is not None else None
+        flat = None
+        if staged is not None and list(staged[1]) == depth_ids:
+            held = staged[0].buf.get("depth") if isinstance(staged[0], Staging) else staged[0]
+            if torch.is_tensor(held) and held.is_pinned() and held.numel() * held.element_size() >= each * len(frames):
+                flat = held.view(-1).view(torch.uint8)[:each * len(frames)]
+        if flat is None:
+            stage = staging.get("depth", each * len(frames))
+            if host_lib().bff_host_pack_frames(frames, stage.data_ptr(), each, n_threads) != len(frames):
+                return None
+            flat = stage[:each * len(frames)]
+        if raw_depth is not None:
+            from .io import bilinear_taps
+            hs, ws_ = f0.shape
+            raw_dev = flat.view(torch.int16).view(len(frames), hs, ws_).to(dev, non_blocking=True)
+            if keep_raw_depth(n, h, w):              # resident at the sensor's resolution: the sweep resizes per point
+                depth_dev, raw_keep = None, raw_dev
+                if tile_raw_depth():
+                    raw_keep, raw_size = _lib.tile_depth(raw_dev, metres=tile_raw_depth() == "f32"), (hs, ws_)
+            else:
+                taps = None
+                if (hs, ws_) != (h, w):
+                    taps = _taps_cache(hs, ws_, h, w, dev)
+                depth_dev = _lib.depth_from_u16(raw_dev, h, w, taps)
+        else:
+            depth_dev = flat.view(torch.float32).view(len(frames), h * w).to(dev, non_blocking=True)
+    else:
+        depth_dev = torch.zeros((0, h * w), dtype=torch.float32, device=dev)
+    return depth_dev, raw_keep, raw_size
+
+
+def _cloud_to_device(pts, n, stride, n_pad, dev, staging):
+    """float64 [n][stride] cloud -> (xyz [3][n_pad] sorted along the Morton curve, unsort, perm, sorted?, tile bounds),
+    everything enqueued on the current stream (bff_cloud_layout)."""
+    pstage = staging.get("points", pts.nbytes)
+    np.copyto(pstage.numpy()[:pts.nbytes].view(np.float64).reshape(n, stride), pts)
+    pts_dev = pstage[:pts.nbytes].view(torch.float64).view(n, stride).to(dev, non_blocking=True)
+    xyz = torch.empty((3, n_pad), dtype=torch.float64, device=dev)
+    unsort = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    sort = n > 1
+    perm = None
+    if n:
+        perm = torch.empty(n, dtype=torch.int32, device=dev)
+        codes = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        box = torch.empty(6, dtype=torch.float64, device=dev)
+        need = ctypes.c_size_t(0)
+        _lib.call("bff_cloud_layout", None, n, stride, n_pad, 1, None, None, None, None, None, None, ctypes.byref(need))
+        temp = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+        nbytes = ctypes.c_size_t(temp.numel())
+        _lib.call("bff_cloud_layout", _lib._ptr(pts_dev), n, stride, n_pad, 1 if sort else 0, _lib._ptr(xyz), _lib._ptr(unsort),
+                  _lib._ptr(perm), _lib._ptr(codes), _lib._ptr(box), _lib._ptr(temp), ctypes.byref(nbytes))
+    else:
+        xyz.zero_()
+    bounds = _lib.point_tile_bounds(xyz, n) if n else None
+    return xyz, unsort, perm, sort, bounds
+
+
+def prepare_geometry_fast(scene, cfg, mask_2ds, device="cuda", with_viewed=True, staging: Staging = None,
+                          n_threads=4) -> SceneGeometry:
+    """scene.prepare_geometry with prepare_scene_fast's byte work: depth frames (the union of the classes' mask frames,
+    then the viewed frames) through pinned staging in one copy, poses inverted in one batched call, the cloud laid out
+    on the device, and the viewed counts (bff_count_viewed) -- all enqueued on the current stream."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return prepare_geometry(scene, cfg, mask_2ds, device=device, with_viewed=with_viewed)
+    staging = staging or Staging()
+    staging.wait()
+    h, w = int(cfg.height_2d), int(cfg.width_2d)
+    pts = np.asarray(scene.points)
+    if pts.dtype != np.float64 or pts.ndim != 2 or pts.shape[1] < 3 or not pts.flags.c_contiguous:
+        pts = np.ascontiguousarray(pts[:, :3], dtype=np.float64)
+    n, stride = pts.shape
+    n_pad = max(1024, ((n + 1023) // 1024) * 1024)
+    viewed = _viewed_ids_cached(scene, cfg.downsample_ratio) if with_viewed else []
+    ids = frame_union(mask_2ds, viewed)
+    inv = np.linalg.inv(np.stack([np.asarray(scene.poses[f], dtype=np.float64) for f in ids])).reshape(len(ids), 16) \
+        if ids else np.zeros((0, 16))
+    got = _depth_to_device(scene, ids, n, h, w, dev, staging, n_threads)
+    if got is None:
+        return prepare_geometry(scene, cfg, mask_2ds, device=device, with_viewed=with_viewed)
+    depth_dev, raw_keep, raw_size = got
+    xyz, unsort, perm, sort, bounds = _cloud_to_device(pts, n, stride, n_pad, dev, staging)
+    geom = SceneGeometry(scene_id=scene.scene_id, n_points=n, nw=(n + 63) // 64, height=h, width=w,
+                         cam_intr=np.asarray(scene.cam_intr, dtype=np.float64)[:3, :3].copy(), xyz=xyz, frame_ids=ids,
+                         inv_pose_host=inv, depth=depth_dev, depth_raw=raw_keep, depth_size=raw_size, tile_bounds=bounds,
+                         unsort=unsort[:n] if sort else None, perm=perm if sort else None, n_viewed=len(viewed),
+                         stage1=getattr(scene, "stage1", None))
+    if with_viewed:
+        count_geometry_viewed(geom, viewed)
+    staging.fence()
+    return geom
+
+
+def prepare_class_fast(geom: SceneGeometry, mask_2d, cfg, staging: Staging = None, n_threads=4) -> DeviceScene:
+    """scene.prepare_class with the run tables built natively into pinned staging and the small tables (frame table,
+    label ids, inverse poses) uploaded as one block; only the class's own data crosses the bus."""
+    dev = geom.xyz.device
+    if dev.type != "cuda":
+        return prepare_class(geom, mask_2d, cfg)
+    staging = staging or Staging()
+    staging.wait()
+    h, w = geom.height, geom.width
+    nb = lambda x: torch.as_tensor(x).to(dev, non_blocking=True)
+    word_bits = class_word_bits(mask_2d)
+    slots, f_mask, f_rowbase, f_nmask, vmo, all_rles, conf_list, labels, n_rows = \
+        class_frame_table(mask_2d, word_bits, geom.slot)
+    packed = pack_rles(all_rles, h * w, staging, "m2d", n_threads) if all_rles else None
+    if all_rles and packed is None:
+        return prepare_class(geom, mask_2d, cfg)                    # rare inputs: exact slow path
+    if packed is None:
+        z = torch.zeros(0, dtype=torch.int32)
+        packed = (z, z, torch.zeros(1, dtype=torch.int32))
+    run_start, run_end, run_offs = (nb(t) for t in packed)
+    conf_d = None
+    if conf_list:
+        dts = {c.dtype for c in conf_list}
+        if len(dts) != 1:
+            raise TypeError(f"mixed confidence dtypes {dts}")
+        if all(c.device.type == "cpu" and c.is_contiguous() for c in conf_list):
+            esz = conf_list[0].element_size()
+            meta = np.empty((2, len(conf_list)), dtype=np.int64)
+            meta[0] = [c.data_ptr() for c in conf_list]
+            meta[1] = [c.numel() * esz for c in conf_list]
+            total = int(meta[1].sum())
+            cstage = staging.get("conf", total)
+            if host_lib().bff_host_gather_bytes(meta[0].ctypes.data, meta[1].ctypes.data, len(conf_list), cstage.data_ptr()) != total:
+                raise ValueError("confidence tensors could not be gathered")
+            conf_d = cstage[:total].view(conf_list[0].dtype).to(dev, non_blocking=True)
+        else:
+            conf_d = torch.cat([c.reshape(-1) for c in conf_list]).to(dev)
+    else:
+        conf_d = torch.zeros(0, dtype=torch.float16, device=dev)
+    ids = {s: k for k, s in enumerate(dict.fromkeys(labels))}
+    label_id = np.zeros(len(labels), dtype=np.int32) if len(ids) <= 1 else \
+        np.fromiter(map(ids.__getitem__, labels), dtype=np.int32, count=len(labels))
+    nf = len(slots)
+    inv = geom.inv_pose_host[np.array(slots, dtype=np.int64)] if nf else np.zeros((0, 16))
+    tables = [np.asarray(a, dtype=np.int32) for a in (slots, f_mask, f_rowbase, f_nmask, np.zeros(nf, np.int32), vmo)] + [label_id]
+    sizes = [t.size for t in tables]
+    tstage = staging.get("tables", 4 * sum(sizes) + 8 * inv.size + 64).numpy()
+    np.concatenate(tables, out=tstage[:4 * sum(sizes)].view(np.int32))
+    at = (4 * sum(sizes) + 7) // 8 * 8
+    tstage[at:at + 8 * inv.size].view(np.float64)[:] = inv.reshape(-1)
+    tdev = staging.buf["tables"][:at + 8 * inv.size].to(dev, non_blocking=True)
+    tint = tdev[:4 * sum(sizes)].view(torch.int32)
+    cuts = np.cumsum([0] + sizes)
+    d_idx_d, f_mask_d, f_rowbase_d, f_nmask_d, f_flags_d, vmo_d, label_d = (tint[cuts[k]:cuts[k + 1]] for k in range(7))
+    inv_d = tdev[at:at + 8 * inv.size].view(torch.float64).view(nf, 16)
+    staging.fence()
+    return DeviceScene(
+        scene_id=geom.scene_id, n_points=geom.n_points, nw=geom.nw, height=h, width=w, cam_intr=geom.cam_intr, xyz=geom.xyz,
+        tile_bounds=geom.tile_bounds, depth=geom.depth, inv_pose=inv_d, depth_index=d_idx_d, frame_mask=f_mask_d,
+        frame_rowbase=f_rowbase_d, frame_nmask=f_nmask_d, frame_flags=f_flags_d, n_frames=nf, n_mask_frames=nf,
+        n_viewed=geom.n_viewed, word_bits=word_bits, n_rows=n_rows, run_start=run_start, run_end=run_end,
+        mask_run_offs=run_offs, view_mask_offs=vmo_d, conf=conf_d, labels=labels, label_id=label_d,
+        n_label_ids=max(1, len(ids)), stage1=geom.stage1, unsort=geom.unsort, perm=geom.perm, depth_raw=geom.depth_raw,
+        depth_size=geom.depth_size, viewed_in=geom.viewed, geometry=geom)
 
 def _viewed_ids_cached(scene, ratio):
     """scene.viewed_frame_ids (a sort of the ~3000 colour file names by their number) once per scene object."""
@@ -416,6 +536,34 @@ class Ingestor:
 
     def submit(self, scene):
         return self.pool.submit(self._work, scene)
+
+    def _work_classes(self, item, classes):
+        """One scene for several classes: (SceneGeometry, [DeviceScene per class], ready event)."""
+        tl = self.local
+        if not hasattr(tl, "stream"):
+            torch.cuda.set_device(self.device)
+            tl.stream = torch.cuda.Stream(device=self.device)
+            tl.staging = Staging()
+        if callable(item):                            # e.g. io.load_scene_classes of one scene
+            try:
+                item = item(staging=tl.staging)
+            except TypeError:
+                item = item()
+        masks = [item.masks[c] for c in classes]
+        if not hasattr(tl, "class_staging"):
+            tl.class_staging = Staging()              # the classes' small tables do not wait for the scene's depth copy
+        with torch.cuda.stream(tl.stream):
+            geom = prepare_geometry_fast(item.scene, self.cfg, masks, self.device, self.with_viewed, tl.staging,
+                                         self.native_threads)
+            dss = [prepare_class_fast(geom, m, self.cfg, tl.class_staging, self.native_threads) for m in masks]
+            ev = torch.cuda.Event()
+            ev.record()
+        return geom, dss, ev
+
+    def submit_classes(self, item, classes):
+        """`item`: a scene.SceneClasses or a callable that loads one (on the loader thread); `classes`: the classes to
+        prepare, in order.  Future of (SceneGeometry, [DeviceScene], ready event)."""
+        return self.pool.submit(self._work_classes, item, classes)
 
     def close(self):
         self.pool.shutdown(wait=True)

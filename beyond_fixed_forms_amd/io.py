@@ -165,6 +165,47 @@ def load_scene(cfg, cls: str, scene_id: str, depth_on_device: bool = False, stag
                        mask_2d=mask_2d, color_files=color_files, height=h, width=w)
 
 
+def load_scene_classes(cfg, classes, scene_id: str, depth_on_device: bool = False, staging=None):
+    """load_scene for several query classes of one scene: the cloud, the poses and the depth frames are read ONCE --
+    every frame any class's mask list names, then the detection-ratio sweep's frames -- plus each class's
+    mask_2d/<cls>/<scene>.pth.  -> scene.SceneClasses (its `scene` holds an empty mask_2d)."""
+    from .scene import SceneClasses, frame_union, viewed_frame_ids
+    scene_dir = os.path.join(cfg.scene_2d_dir, scene_id)
+    cam_intr = read_matrix_txt(os.path.join(scene_dir, "intrinsic", "intrinsic_color.txt"))     # P:376
+    points = np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"))                         # P:387
+    masks = {cls: torch.load(os.path.join(cfg.mask_2d_dir, cls, f"{scene_id}.pth"), weights_only=False)   # P:396
+             for cls in classes}
+    color_dir = os.path.join(scene_dir, "color")
+    color_files = [f for f in os.listdir(color_dir) if f.endswith(".jpg")] if os.path.isdir(color_dir) else []
+    viewed = viewed_frame_ids(color_files, cfg.downsample_ratio) \
+        if (not cfg.if_occurance_threshold) and cfg.if_detected_ratio_threshold else []
+    need = frame_union([masks[c] for c in classes], viewed)          # the geometry's slot order (upload order)
+    w, h = int(cfg.width_2d), int(cfg.height_2d)
+    poses = {f: read_matrix_txt(os.path.join(scene_dir, "pose", f"{f}.txt")) for f in need}      # P:422
+    if depth_on_device:
+        paths = [os.path.join(scene_dir, "depth", f"{f}.png") for f in need]
+        out = None
+        if staging is not None and need:
+            import ctypes
+            from .ingest import host_lib
+            hw = (ctypes.c_int32 * 2)()
+            if host_lib().bff_host_png_size(paths[0].encode(), ctypes.cast(hw, ctypes.c_void_p)) == 0:
+                staging.wait()
+                nbytes = 2 * len(need) * int(hw[0]) * int(hw[1])
+                out = staging.get("depth", nbytes).numpy()[:nbytes].view(np.uint16)
+        frames = decode_depth_pngs(paths, out=out)
+        scene = SceneInputs(scene_id=scene_id, points=points, cam_intr=cam_intr, poses=poses, depths={},
+                            depths_raw={f: frames[i] for i, f in enumerate(need)},
+                            mask_2d=[], color_files=color_files, height=h, width=w)
+        if out is not None:
+            scene.depth_staged = (staging, list(need))
+    else:
+        depths = {f: load_depth(os.path.join(scene_dir, "depth", f"{f}.png"), w, h) for f in need}   # P:431-436
+        scene = SceneInputs(scene_id=scene_id, points=points, cam_intr=cam_intr, poses=poses, depths=depths,
+                            mask_2d=[], color_files=color_files, height=h, width=w)
+    return SceneClasses(scene, masks)
+
+
 def scene_checkpoint_file(stage: str, cls: str) -> str:
     """P:320-322 / R:41-43."""
     return f"checkpoints/{stage}_checkpoint_{cls}.yaml"

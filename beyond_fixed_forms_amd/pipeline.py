@@ -302,8 +302,9 @@ class SceneWorkspace:
         return self.t[name][:n].view(*shape)
 
 
-def issue(ds, cfg, depth_thresh, stage1=None, n_frames=None):
-    """Enqueue the whole device side of one scene on the current stream.  Returns a handle for `collect`."""
+def issue(ds, cfg, depth_thresh, stage1=None, n_frames=None, viewed_in=None):
+    """Enqueue the whole device side of one scene on the current stream.  Returns a handle for `collect`.
+    viewed_in: the detection ratio's viewed counts, computed beforehand (bff_scene_project_viewed; SceneGeometry)."""
     t0 = time.perf_counter() if _TRACE_ISSUE else 0.0
     dev = ds.xyz.device
     key = (id(stage1), n_frames)
@@ -334,13 +335,17 @@ def issue(ds, cfg, depth_thresh, stage1=None, n_frames=None):
     pr = params_struct(cfg, depth_thresh, filter_sort=use_sort)
     ws.in_flight = True
     t1 = time.perf_counter() if _TRACE_ISSUE else 0.0
-    _lib.call("bff_scene_project", ctypes.byref(sc), ctypes.byref(pr), ctypes.byref(ws.struct))
+    if viewed_in is None:
+        _lib.call("bff_scene_project", ctypes.byref(sc), ctypes.byref(pr), ctypes.byref(ws.struct))
+    else:
+        _lib.call("bff_scene_project_viewed", ctypes.byref(sc), ctypes.byref(pr), ctypes.byref(ws.struct),
+                  _lib._ptr(viewed_in, torch.int32))
     if _TRACE_ISSUE and time.perf_counter() - t0 > 2e-3:      # the one-time stalls of a process's first scene calls
         import sys
         now = time.perf_counter()
         print(f"slow issue: {1e3 * (now - t0):.2f} ms, of which the native call {1e3 * (now - t1):.2f} ms", file=sys.stderr)
     return dict(ws=ws, both=both, s1_rows=s1_rows, params=pr, stream=ws.stream, cap=cap,
-                args=(ds, cfg, depth_thresh, stage1, n_frames))
+                args=(ds, cfg, depth_thresh, stage1, n_frames, viewed_in))
 
 
 def collect(h):
@@ -435,6 +440,72 @@ def project_stream(scenes, cfg, device, consume, n_loaders=2, with_stage1=True, 
         fr, st1 = h
         with _lib.on_stream(streams[i % depth]):
             consume(i, st1, projection_back(fr, want_groups=want_groups))
+
+    try:
+        for _ in pipelined(n, front, back, depth):
+            pass
+    finally:
+        ing.close()
+
+
+def project_classes_stream(items, cfg, device, consume, n_loaders=2, depth=None, want_groups=False):
+    """project_stream for several query classes per scene: the projection stage of every (scene, class) pair, scenes in
+    order and, inside a scene, its classes in order.  `items`: a list of (source, classes) -- source a scene.SceneClasses
+    or a zero-argument callable that loads one (io.load_scene_classes; called on a loader thread), classes the class names
+    to project for that scene.  A loader reads the scene once and prepares, on its own stream, the scene's geometry
+    (cloud, poses, depth, viewed counts: scene.SceneGeometry) and every class's tables; the pairs then go through the
+    same PIPELINE_DEPTH streams and workspaces as project_stream.  Each class's result is bit-identical to project_stream
+    over that class's own scenes.  `consume(k, cls, None, Stage2Result)` is called in pair order on the pair's stream
+    (k = index into `items`).  A scene's geometry stays alive until the last of its classes has been consumed."""
+    from .ingest import Ingestor
+    from .projection import projection_back, projection_front
+    from .scene import prepare_class, prepare_geometry, with_viewed_counts
+    dev = torch.device(device)
+    depth = PIPELINE_DEPTH if depth is None else depth
+    pairs = [(k, j, c) for k, (_src, classes) in enumerate(items) for j, c in enumerate(classes)]
+    n = len(pairs)
+    if n == 0:
+        return
+    with_viewed = with_viewed_counts(cfg)
+    if dev.type != "cuda":                      # host tensors: no streams, no loaders (the kernels themselves need the GPU)
+        for k, (src, classes) in enumerate(items):
+            sc = src() if callable(src) else src
+            masks = [sc.masks[c] for c in classes]
+            geom = prepare_geometry(sc.scene, cfg, masks, device=device, with_viewed=with_viewed)
+            for c, m in zip(classes, masks):
+                consume(k, c, None, projection_back(projection_front(prepare_class(geom, m, cfg), cfg),
+                                                    want_groups=want_groups))
+        return
+    streams = scene_streams(dev, depth)
+    ing = Ingestor(cfg, dev, n_loaders=n_loaders, with_viewed=with_viewed, with_stage1=False)
+    n_items = len(items)
+    lookahead = max(1, depth // 2) + n_loaders   # scenes ahead (each holds its geometry and class tables)
+    futs = {k: ing.submit_classes(items[k][0], list(items[k][1])) for k in range(min(lookahead, n_items))}
+    ready = {}                                  # scene -> (geometry, [DeviceScene], event) while it has classes left
+    left = {k: len(items[k][1]) for k in range(n_items)}
+    submitted = [min(lookahead, n_items)]
+
+    def front(i):
+        k, j, c = pairs[i]
+        if k not in ready:
+            ready[k] = futs.pop(k).result()
+            if submitted[0] < n_items:
+                futs[submitted[0]] = ing.submit_classes(items[submitted[0]][0], list(items[submitted[0]][1]))
+                submitted[0] += 1
+        geom, dss, ev = ready[k]
+        ds = dss[j]
+        left[k] -= 1
+        if left[k] == 0:
+            del ready[k]                        # the class scenes keep the geometry alive until they are consumed
+        st = streams[i % depth]
+        st.wait_event(ev)                       # the uploads and the viewed counts ran on the loader's stream
+        with _lib.on_stream(st):
+            return projection_front(ds, cfg), k, c
+
+    def back(i, h):
+        fr, k, c = h
+        with _lib.on_stream(streams[i % depth]):
+            consume(k, c, None, projection_back(fr, want_groups=want_groups))
 
     try:
         for _ in pipelined(n, front, back, depth):

@@ -199,19 +199,27 @@ def projection_front(ds: DeviceScene, cfg, debug_out: bool = False, timers=None,
     and components are issued one by one and `projection_back` continues on the host."""
     if fast is None:
         fast = not debug_out
+    do_ratio = (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
+    # one class of a multi-class run (scene.prepare_class): the viewed counts were computed once for the scene
+    viewed_in = ds.viewed_in if do_ratio else None
+    if do_ratio and ds.geometry is not None and viewed_in is None:
+        raise ValueError("a class scene needs its geometry's viewed counts for the detection-ratio filter "
+                         "(prepare the geometry with with_viewed=True)")
     if fast and fast_path_ok(ds) and (stage1 is None or stage1.n_points == ds.n_points):
-        do_ratio = (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
         fr = _Front(ds, cfg, {}, False, do_ratio=do_ratio, stage1=stage1)
         with sweep_span(timers, "project_views"), merge_span(timers, "merge_components"):
-            fr.fast = pipeline.issue(ds, cfg, DEPTH_THRESH, stage1, ds.n_frames if do_ratio else ds.n_mask_frames)
+            fr.fast = pipeline.issue(ds, cfg, DEPTH_THRESH, stage1,
+                                     ds.n_frames if (do_ratio and viewed_in is None) else ds.n_mask_frames, viewed_in)
         return fr
     with _lib.launch_stream():
-        fr = _projection_front(ds, cfg, debug_out, timers)
+        fr = _projection_front(ds, cfg, debug_out, timers, viewed_in=viewed_in)
         fr.stage1 = stage1
         return fr
 
 
-def _projection_front(ds, cfg, debug_out, timers) -> _Front:
+def _projection_front(ds, cfg, debug_out, timers, viewed_in=None) -> _Front:
+    """viewed_in (detection-ratio filter only): the viewed counts of the scene, computed beforehand (bff_count_viewed);
+    the sweep then visits the mask frames alone and counts no visibility."""
     dev = ds.xyz.device
     fr = _Front(ds, cfg, {}, debug_out)
     n, nw = ds.n_points, ds.nw
@@ -236,15 +244,20 @@ def _projection_front(ds, cfg, debug_out, timers) -> _Front:
         else:
             rows = fr.rows = torch.zeros((ds.n_rows, nw), dtype=torch.int64, device=dev)
     masked = fr.masked = torch.zeros(n, dtype=torch.int32, device=dev)                          # P:402
-    viewed = fr.viewed = torch.zeros(n, dtype=torch.int32, device=dev) if do_ratio else None    # P:537
-    n_frames = ds.n_frames if do_ratio else ds.n_mask_frames
+    if do_ratio and viewed_in is not None:
+        viewed, sweep_viewed, n_frames = viewed_in, None, ds.n_mask_frames
+        fr.viewed = viewed
+    else:
+        viewed = fr.viewed = torch.zeros(n, dtype=torch.int32, device=dev) if do_ratio else None    # P:537
+        sweep_viewed = viewed
+        n_frames = ds.n_frames if do_ratio else ds.n_mask_frames
     # the sweep flags, per row, the 512-point chunks it stores into: the later passes read nothing else
     cmask_in = fr.cmask = _lib.chunk_mask_buffer(ds.n_rows, nw, dev).zero_() if (ds.n_rows and n_mviews) else None
     with sweep_span(timers, "project_views"):
         _lib.project_views(ds.xyz, n, ds.inv_pose[:n_frames], ds.cam_intr, ds.sweep_depth, ds.depth_index, ds.height,
                            ds.width, DEPTH_THRESH, maskbits if n_mviews else None, ds.word_bits, ds.frame_mask,
                            ds.frame_rowbase, ds.frame_nmask, ds.frame_flags, rows if ds.n_rows else None,
-                           masked, viewed, segmap if n_mviews else None, cmask_in, ds.tile_bounds, depth_size=ds.depth_size)
+                           masked, sweep_viewed, segmap if n_mviews else None, cmask_in, ds.tile_bounds, depth_size=ds.depth_size)
     del maskbits
     # a14/a15: point filter (P:512-583), entirely on the device: the threshold never visits the host
     if cfg.if_occurance_threshold or do_ratio:
@@ -323,7 +336,8 @@ def _fast_back(fr: _Front, stage1, want_groups) -> Stage2Result:
         mw = max(_lib.load().bff_chunk_mask_words(nw), 1)
         hd = ws.t["hdr"]
         slow = _Front(ds, cfg, dbg, False, rows=ws.view("rows", ds.n_rows, nw), masked=ws.view("masked", n),
-                      viewed=ws.view("viewed", n) if fr.do_ratio else None, keep=ws.view("keep", nw),
+                      viewed=(ds.viewed_in if ds.viewed_in is not None else ws.view("viewed", n)) if fr.do_ratio else None,
+                      keep=ws.view("keep", nw),
                       thr_dev=hd[HDR_THR:HDR_THR + 1].view(torch.float32) if filtered else None,
                       lat_info=hd[HDR_NUNIQUE:HDR_NUNIQUE + 1] if filtered else None,
                       area=ws.view("area", ds.n_rows), comp=ws.view("comp", ds.n_rows),
@@ -527,3 +541,31 @@ def project_scene(scene, cfg, device="cuda", return_result: bool = False, debug_
         ds = prepare_scene(scene, cfg, device=device, with_viewed=with_viewed)
     res = run_projection(ds, cfg, debug_out=debug_out)
     return res if return_result else res.to_dict()
+
+
+def project_scene_classes(scene, masks: dict, cfg, device="cuda", return_result: bool = False, debug_out: bool = False,
+                          raw_depth_resident=None):
+    """project_scene for several query classes of one scene: {cls: mask_2d} -> {cls: the dict saved at P:630-634}.
+    The cloud, the poses and the depth are uploaded once and the detection ratio's viewed counts are computed once
+    (scene.SceneGeometry); each class then uploads its own masks and runs the single-class device path against them.
+    Every class's result is bit-identical to project_scene on a scene whose mask_2d is that class's list.
+    raw_depth_resident (plain preparation only, i.e. debug_out or a CPU device): as scene.prepare_scene."""
+    _lib.load()
+    from .scene import prepare_class, prepare_geometry, with_viewed_counts
+    classes = list(masks)
+    lists = [masks[c] for c in classes]
+    with_viewed = with_viewed_counts(cfg)
+    fast = torch.device(device).type == "cuda" and not debug_out and raw_depth_resident is None
+    if fast:
+        from .ingest import prepare_class_fast, prepare_geometry_fast
+        geom = prepare_geometry_fast(scene, cfg, lists, device=device, with_viewed=with_viewed)
+        prep = lambda m: prepare_class_fast(geom, m, cfg)
+    else:
+        geom = prepare_geometry(scene, cfg, lists, device=device, with_viewed=with_viewed,
+                                raw_depth_resident=raw_depth_resident)
+        prep = lambda m: prepare_class(geom, m, cfg)
+    out = {}
+    for c, m in zip(classes, lists):
+        res = run_projection(prep(m), cfg, debug_out=debug_out)
+        out[c] = res if return_result else res.to_dict()
+    return out

@@ -9,7 +9,7 @@ to dense (M,1,H,W) tensors.
 from __future__ import annotations
 
 import dataclasses
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -119,6 +119,10 @@ class DeviceScene:
                                                # in 8 x 8 tiles, int16 or float32 metres; the sweep evaluates the bilinear
                                                # resize (and / 1000 for int16) per point (P:432-436)
     depth_size: Optional[tuple] = None         # (hs, ws) of the tiled frames
+    # one class of a multi-class run (prepare_class): the detection ratio's denominator, counted once for the scene by
+    # SceneGeometry (int32 [N], sorted point order); the sweep then visits the class's mask frames only
+    viewed_in: Optional[torch.Tensor] = None
+    geometry: Optional["SceneGeometry"] = None   # the resident scene whose cloud, poses and depth this one shares
 
     @property
     def sweep_depth(self):
@@ -302,3 +306,216 @@ def prepare_scene(scene, cfg, device="cuda", with_viewed=True, sort_points=True,
         conf=conf.to(dev), labels=labels, label_id=t(label_id, torch.int32), n_label_ids=max(1, len(ids)),
         stage1=getattr(scene, "stage1", None), unsort=None if unsort is None else t(unsort, torch.int32),
         perm=None if perm is None else t(perm.astype(np.int32), torch.int32), depth_raw=raw_keep, depth_size=raw_size)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Several query classes of one scene (pipeline.project_classes_stream, projection.project_scene_classes): the cloud, the
+# poses, the depth frames and the detection ratio's viewed counts depend on the scene alone (P:538-567 never looks at a
+# mask), so they are prepared once (SceneGeometry) and every class adds only its run tables, confidences and labels
+# (prepare_class).  Each class's result is bit-identical to prepare_scene + the single-class path on that class's scene.
+
+@dataclasses.dataclass
+class SceneGeometry:
+    """One scene resident for many classes: sorted cloud, one inverse pose and one depth slot per frame id (the union of
+    the classes' mask frames, in class then list order, then the viewed frames), and the viewed counts."""
+    scene_id: str
+    n_points: int
+    nw: int
+    height: int
+    width: int
+    cam_intr: np.ndarray                 # (3,3) float64, host
+    xyz: torch.Tensor                    # f64 [3][n_pad], sorted
+    frame_ids: List[str]                 # slot k <-> frame id
+    inv_pose_host: np.ndarray            # f64 [slots][16], np.linalg.inv of each pose (P:425)
+    depth: Optional[torch.Tensor]        # as DeviceScene.depth / depth_raw / depth_size, one frame per slot
+    depth_raw: Optional[torch.Tensor] = None
+    depth_size: Optional[tuple] = None
+    tile_bounds: Optional[torch.Tensor] = None
+    unsort: Optional[torch.Tensor] = None
+    perm: Optional[torch.Tensor] = None
+    n_viewed: int = 0                    # frames of the detection-ratio sweep
+    viewed: Optional[torch.Tensor] = None   # i32 [N] viewed counts in the sorted point order (None: no ratio filter)
+    stage1: Optional[dict] = None
+
+    def __post_init__(self):
+        self.slot = {f: k for k, f in enumerate(self.frame_ids)}
+
+    @property
+    def sweep_depth(self):
+        return self.depth_raw if self.depth_raw is not None else self.depth
+
+
+@dataclasses.dataclass
+class SceneClasses:
+    """One scene's inputs for several query classes: `scene` is SceneInputs-like (its own mask_2d is not used), `masks`
+    maps each class to its mask_2d list (io.load_scene_classes)."""
+    scene: object
+    masks: Dict[str, list]
+
+
+def frame_union(mask_2ds, viewed_ids=()):
+    """Frame ids of several mask_2d lists (in list order, list after list), then the viewed frames: each id once."""
+    ids = [fr["frame_id"][:-4] for m in mask_2ds for fr in m]
+    return list(dict.fromkeys(ids + list(viewed_ids)))
+
+
+def class_word_bits(mask_2d):
+    """32-bit mask words unless some frame of the class holds more than 32 masks (chosen per class, as prepare_scene)."""
+    max_m = max((len(fr["segmented_frame_masks"]) for fr in mask_2d), default=0)
+    return 32 if max_m <= 32 else 64
+
+
+def class_frame_table(mask_2d, word_bits, slot_of):
+    """prepare_scene's frame table of the mask frames alone (frame_flags all 0: the viewed counts come from the
+    geometry): (slots, f_mask, f_rowbase, f_nmask, view_mask_offs, rles, conf_list, labels, n_rows)."""
+    slots, f_mask, f_rowbase, f_nmask = [], [], [], []
+    all_rles, view_mask_offs, conf_list, labels = [], [0], [], []
+    row = 0
+    for fr in mask_2d:
+        fid = fr["frame_id"][:-4]
+        rles = fr["segmented_frame_masks"]
+        m = len(rles)
+        if not (len(fr["confidences"]) == m and len(fr["labels"]) == m):
+            raise ValueError(f"frame {fid}: masks / confidences / labels differ in length")
+        s = slot_of[fid]
+        for c0 in range(0, m, word_bits):
+            mc = min(word_bits, m - c0)
+            slots.append(s)
+            f_mask.append(len(view_mask_offs) - 1); f_rowbase.append(row); f_nmask.append(mc)
+            view_mask_offs.append(view_mask_offs[-1] + mc)
+            row += mc
+        all_rles += list(rles)
+        conf_list.append(fr["confidences"])
+        labels += list(fr["labels"])
+    return slots, f_mask, f_rowbase, f_nmask, view_mask_offs, all_rles, conf_list, labels, row
+
+
+def with_viewed_counts(cfg) -> bool:
+    """The detection-ratio filter (P:524-578) is the one that needs viewed counts."""
+    return (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
+
+
+def count_geometry_viewed(geom: SceneGeometry, viewed_ids, depth_thresh=DEPTH_THRESH):
+    """geom.viewed = visibility counts over `viewed_ids` (bff_count_viewed, on the current stream)."""
+    from . import _lib
+    dev = geom.xyz.device
+    geom.n_viewed = len(viewed_ids)
+    viewed = torch.zeros(max(geom.n_points, 1), dtype=torch.int32, device=dev)[:geom.n_points]
+    if viewed_ids and geom.n_points:
+        idx = np.array([geom.slot[f] for f in viewed_ids], dtype=np.int64)
+        inv = torch.as_tensor(np.ascontiguousarray(geom.inv_pose_host[idx])).to(dev, non_blocking=False)
+        d_idx = torch.as_tensor(idx.astype(np.int32)).to(dev)
+        _lib.count_viewed(geom.xyz, geom.n_points, inv, geom.cam_intr, geom.sweep_depth, d_idx, geom.height, geom.width,
+                          depth_thresh, viewed, tile_bounds=geom.tile_bounds, depth_size=geom.depth_size)
+    geom.viewed = viewed
+
+
+def prepare_geometry(scene, cfg, mask_2ds, device="cuda", with_viewed=True, sort_points=True,
+                     raw_depth_resident=None) -> SceneGeometry:
+    """The class-independent part of prepare_scene for the classes whose mask lists are `mask_2ds`: cloud (sorted),
+    inverse poses and depth of every frame any of them or the detection-ratio sweep looks at, and -- with_viewed, on a
+    GPU -- the viewed counts (bff_count_viewed).  Same conversions and layout rules as prepare_scene."""
+    dev = torch.device(device)
+    h, w = int(cfg.height_2d), int(cfg.width_2d)
+    pts = np.asarray(scene.points)[:, :3].astype(np.float64, copy=False)
+    n = pts.shape[0]
+    n_pad = max(1024, ((n + 1023) // 1024) * 1024)
+    soa = np.zeros((3, n_pad), dtype=np.float64)
+    unsort = perm = None
+    if sort_points and n > 1:
+        perm = morton_order(pts)
+        soa[:, :n] = pts[perm].T
+        unsort = np.empty(n, dtype=np.int32)
+        unsort[perm] = np.arange(n, dtype=np.int32)
+    else:
+        soa[:, :n] = pts.T
+    viewed = viewed_frame_ids(scene.color_files, cfg.downsample_ratio) if with_viewed else []
+    ids = frame_union(mask_2ds, viewed)
+    inv = np.stack([np.linalg.inv(np.asarray(scene.poses[f], dtype=np.float64)).reshape(16) for f in ids]) if ids \
+        else np.zeros((0, 16))
+    raw_depth = getattr(scene, "depths_raw", None)
+    raw_keep = raw_size = None
+    if raw_depth is not None and ids:
+        from . import _lib
+        from .io import bilinear_taps
+        frames = []
+        for f in ids:
+            d = np.asarray(raw_depth[f])
+            if d.dtype != np.uint16 or d.ndim != 2:
+                raise ValueError(f"raw depth {f}: expected a 2-D uint16 array")
+            frames.append(d)
+        hs, ws = frames[0].shape
+        if any(d.shape != (hs, ws) for d in frames):
+            raise ValueError("raw depth frames of different sizes")
+        raw_dev = torch.empty((len(frames), hs, ws), dtype=torch.int16, device=dev)
+        for i, d in enumerate(frames):
+            raw_dev[i].copy_(torch.from_numpy(np.ascontiguousarray(d).view(np.int16)))
+        if keep_raw_depth(n, h, w) if raw_depth_resident is None else raw_depth_resident:
+            depth_dev, raw_keep = None, raw_dev
+            if tile_raw_depth():
+                raw_keep, raw_size = _lib.tile_depth(raw_dev, metres=tile_raw_depth() == "f32"), (hs, ws)
+        else:
+            taps = None
+            if (hs, ws) != (h, w):
+                taps = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in bilinear_taps(hs, ws, h, w))
+            depth_dev = _lib.depth_from_u16(raw_dev, h, w, taps)
+    elif ids:
+        depth_dev = torch.empty((len(ids), h * w), dtype=torch.float32, device=dev)
+        for i, f in enumerate(ids):
+            d = np.asarray(scene.depths[f], dtype=np.float32)
+            if d.shape != (h, w):
+                raise ValueError(f"depth {f}: shape {d.shape} != ({h},{w})")
+            depth_dev[i].copy_(torch.from_numpy(np.ascontiguousarray(d).reshape(-1)))
+    else:
+        depth_dev = torch.zeros((0, h * w), dtype=torch.float32, device=dev)
+    xyz_dev = torch.as_tensor(soa).to(dev)
+    bounds = None
+    if dev.type == "cuda" and n:
+        from . import _lib
+        bounds = _lib.point_tile_bounds(xyz_dev, n)
+    t32 = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+    geom = SceneGeometry(scene_id=scene.scene_id, n_points=n, nw=(n + 63) // 64, height=h, width=w,
+                         cam_intr=np.asarray(scene.cam_intr, dtype=np.float64)[:3, :3].copy(), xyz=xyz_dev, frame_ids=ids,
+                         inv_pose_host=inv, depth=depth_dev, depth_raw=raw_keep, depth_size=raw_size, tile_bounds=bounds,
+                         unsort=t32(unsort), perm=t32(perm), n_viewed=len(viewed), stage1=getattr(scene, "stage1", None))
+    if with_viewed and dev.type == "cuda":
+        count_geometry_viewed(geom, viewed)
+    return geom
+
+
+def prepare_class(geom: SceneGeometry, mask_2d, cfg, device=None) -> DeviceScene:
+    """One class of a scene against its resident geometry: the class's RLE run tables, confidences and labels, and a
+    frame table of its mask frames in list order whose depth_index points into the geometry's depth slots.  Frame,
+    mask, label and confidence tables equal prepare_scene's for the class's own scene (with_viewed=False)."""
+    dev = geom.xyz.device if device is None else torch.device(device)
+    h, w = geom.height, geom.width
+    word_bits = class_word_bits(mask_2d)
+    slots, f_mask, f_rowbase, f_nmask, vmo, all_rles, conf_list, labels, n_rows = \
+        class_frame_table(mask_2d, word_bits, geom.slot)
+    for r in all_rles:
+        if int(r["length"]) != h * w:
+            raise ValueError(f"mask RLE length {r['length']} != H*W = {h * w}")
+    rs, re, roffs = runs_from_rles(all_rles, "2-D mask")
+    if conf_list:
+        dts = {c.dtype for c in conf_list}
+        if len(dts) != 1:
+            raise TypeError(f"mixed confidence dtypes {dts}")
+        conf = torch.cat([c.reshape(-1).cpu() for c in conf_list])
+    else:
+        conf = torch.zeros(0, dtype=torch.float16)
+    ids = {}
+    label_id = np.array([ids.setdefault(s, len(ids)) for s in labels], dtype=np.int32)
+    t = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(dev)
+    nf = len(slots)
+    inv = geom.inv_pose_host[np.array(slots, dtype=np.int64)] if nf else np.zeros((0, 16))
+    return DeviceScene(
+        scene_id=geom.scene_id, n_points=geom.n_points, nw=geom.nw, height=h, width=w, cam_intr=geom.cam_intr,
+        xyz=geom.xyz, tile_bounds=geom.tile_bounds, depth=geom.depth,
+        inv_pose=t(inv.reshape(nf, 16), torch.float64), depth_index=t(np.array(slots, np.int32), torch.int32),
+        frame_mask=t(np.array(f_mask, np.int32), torch.int32), frame_rowbase=t(np.array(f_rowbase, np.int32), torch.int32),
+        frame_nmask=t(np.array(f_nmask, np.int32), torch.int32), frame_flags=t(np.zeros(nf, np.int32), torch.int32),
+        n_frames=nf, n_mask_frames=nf, n_viewed=geom.n_viewed, word_bits=word_bits, n_rows=n_rows,
+        run_start=t(rs, torch.int32), run_end=t(re, torch.int32), mask_run_offs=t(roffs, torch.int32),
+        view_mask_offs=t(np.array(vmo, np.int32), torch.int32), conf=conf.to(dev), labels=labels,
+        label_id=t(label_id, torch.int32), n_label_ids=max(1, len(ids)), stage1=geom.stage1, unsort=geom.unsort,
+        perm=geom.perm, depth_raw=geom.depth_raw, depth_size=geom.depth_size, viewed_in=geom.viewed, geometry=geom)

@@ -298,3 +298,27 @@ def make_text_bank(dim: int = 768, seed: int = 0, dtype=torch.float16):
     bank = torch.randn(len(SCANNET200_LABELS), dim, generator=g)
     bank = (bank / bank.norm(dim=1, keepdim=True)).to(dtype)
     return bank, {lab: i for i, lab in enumerate(SCANNET200_LABELS)}
+
+
+def derive_classes(scene: SceneInputs, k: int = 8, fraction: float = 0.15, seed: int = 0) -> Dict[str, List[dict]]:
+    """K query classes of one scene for multi-class runs: class j keeps a deterministic subset of about `fraction` of the
+    scene's mask_2d frames (at least one, in list order) and labels every mask with its own query string.
+    -> {query: mask_2d list}."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    n = len(scene.mask_2d)
+    for j in range(k):
+        keep = np.flatnonzero(rng.random(n) < fraction)
+        if keep.size == 0 and n:
+            keep = np.array([int(rng.integers(0, n))])
+        query = f"query {j}"
+        out[query] = [dict(scene.mask_2d[i], labels=[query] * len(scene.mask_2d[i]["labels"])) for i in keep]
+    return out
+
+
+def class_scene(scene: SceneInputs, mask_2d: List[dict]) -> SceneInputs:
+    """The same scene with another class's mask list (what the single-class path gets for that class)."""
+    import copy
+    out = copy.copy(scene)
+    out.mask_2d = mask_2d
+    return out

@@ -158,6 +158,20 @@ int bff_project_views_u16(const double *xyz, int64_t n_points, int64_t n_pad,
                           uint64_t *rows, int64_t n_rows, int64_t nw, uint64_t *chunk_mask,
                           int32_t *masked_count, int32_t *viewed_count, const double *tile_bounds, void *stream);
 
+/* The detection-ratio sweep alone (P:538-567), for a frame list that carries no masks: viewed_count[n] += 1 for every
+ * frame f < n_frames in which point n is visible.  Visibility is bff_project_views' bit for bit (the same fma chains,
+ * rint, bounds on the doubles, resize taps and operation order, depth test), so the counts equal what that sweep adds
+ * under frame flag bit 0 -- computed once per scene, they serve every query class of the scene
+ * (bff_scene_project_viewed).  viewed_count is int32 [n_points], NOT cleared here (the caller zeroes it).
+ *   depth_layout -1: depth is float32 [n_depth][height * width] metres (depth_h, depth_w unused); 0, 1, 2: depth is the
+ *                sensor-resolution frames of bff_project_views_u16 in that layout (height + width <= 4096)
+ *   frames_per_block  frames one block visits (its frame tile); 0 = the library's choice
+ *   tile_bounds  optional bff_point_tile_bounds table (exact frustum culling, as bff_project_views) */
+int bff_count_viewed(const double *xyz, int64_t n_points, int64_t n_pad, const double *inv_pose,
+                     const double *cam_intr_host, int32_t n_frames, const void *depth, int32_t depth_h, int32_t depth_w,
+                     int32_t depth_layout, const int32_t *depth_index, int32_t height, int32_t width, double depth_thresh,
+                     int32_t frames_per_block, int32_t *viewed_count, const double *tile_bounds, void *stream);
+
 /* Frustum culling for bff_project_views (optional, exact).  bounds: float64 [ceil(n_points / bff_point_tile_size())][6]
  * = (xmin, ymin, zmin, xmax, ymax, zmax) of every tile of bff_point_tile_size() consecutive points -- the points
  * one wave of the sweep owns.  Given the table, a wave skips a frame when the box of its points cannot contain a
@@ -574,6 +588,12 @@ int32_t bff_scene_struct_bytes(int32_t which);     /* 0 bff_scene, 1 bff_scene_p
  * the host (projection._projection_back), ws->rows is then still intact. */
 int bff_scene_project(const bff_scene *scene, const bff_scene_params *params, const bff_scene_workspace *ws,
                       void *stream);
+/* bff_scene_project with the detection ratio's denominator given: viewed_in int32 [n_points] (the scene's sorted point
+ * order) as bff_count_viewed computes it over the scene's viewed frames.  The sweep then counts no visibility (pass only
+ * the class's mask frames, frame_flags all 0) and the point filter reads viewed_in instead of ws->viewed.  viewed_in ==
+ * NULL is bff_scene_project. */
+int bff_scene_project_viewed(const bff_scene *scene, const bff_scene_params *params, const bff_scene_workspace *ws,
+                             const int32_t *viewed_in, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Ingestion: cloud layout on the device.  pts: float64 [n][stride] exactly as <scene>.npy
