@@ -2516,14 +2516,14 @@ extern "C" int bff_or_reduce_grouped(const uint64_t *rows, int64_t nw, int32_t n
     BFF_REQUIRE(rows && info && offs && members && slices && out, "bff_or_reduce_grouped: null pointer");
     BFF_REQUIRE((conf == nullptr) == (conf_mean == nullptr) && (conf_dtype == 0 || conf_dtype == 1),
                 "bff_or_reduce_grouped: conf and conf_mean go together, dtype 0 (f32) or 1 (f16)");
+    const int slice_cap = bff_group_slice_cap(n_rows, cap);
+    BFF_LIMIT(slice_cap + 1 <= 65535, "bff_or_reduce_grouped: too many member slices");
     hipStream_t st = as_stream(stream);
     if (nw > 0) {
         hipError_t e = zero_async(out, sizeof(uint64_t) * (size_t)cap * nw, st);
         if (e != hipSuccess) return fail((int)e, "bff_or_reduce_grouped: memset: %s", hipGetErrorString(e));
     }
-    const int slice_cap = bff_group_slice_cap(n_rows, cap);
     dim3 grid((unsigned)ceil_div(nw > 0 ? nw : 1, 256), (unsigned)(slice_cap + 1));
-    BFF_LIMIT(slice_cap + 1 <= 65535, "bff_or_reduce_grouped: too many member slices");
     // through the chunk flags only when the rows are long (config 2: the dense pass runs at HBM speed and the flagged
     // form was measured slower; config 4: 4.8 GB of rows, ~1 % occupied)
     const uint64_t *cm = (chunk_mask && nw >= or_sparse_min_words()) ? chunk_mask : nullptr;

@@ -469,7 +469,7 @@ int bff_cosine_rows(const void *a, int32_t na, const void *b, int32_t nb, int32_
 #define BFF_GROUP_CAP_MAX 512     /* ... and the largest capacity a workspace may ask for (bff_scene_workspace.group_cap) */
 #define BFF_SIGNATURE_BITS 30     /* bff_row_stats signatures are 30-bit keys */
 
-/* Device twin of bff_host_component_csr for at most `cap` <= BFF_GROUP_CAP kept groups.  comp[i] = smallest row index
+/* Device twin of bff_host_component_csr for at most `cap` <= BFF_GROUP_CAP_MAX kept groups.  comp[i] = smallest row index
  * of i's component (bff_merge_components) -- an INPUT when parent == NULL; with parent (the disjoint-set forest
  * bff_merge_components leaves behind when called with comp == NULL) comp is an OUTPUT, flattened here on the way.
  * Outputs (device): info[4] = {K kept groups (may exceed cap), flags (bit 0:

@@ -37,6 +37,26 @@ def test_entry_points_reject_bad_arguments_without_a_gpu():
     assert lib.bff_cosine_gemm_f16(None, 1, None, 1, 33, None, None) == -1
     assert lib.bff_rle_to_maskbits(None, None, None, None, 1, 10, 48, None, None, None) == -1
     assert lib.bff_popcount_rows(None, None, 0, 0, None, None) == 0          # empty work is fine
+    # the scene tail's device-count entry points: null pointers and inconsistent sizes, before any memset or launch
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    assert lib.bff_scatter_bits(p, 1, 2, p, 100, 3, p, None, None) == -1 and b"bad sizes" in lib.bff_last_error()
+    assert lib.bff_scatter_bits(p, 1, 2, None, 100, 2, p, None, None) == -1 and b"null pointer" in lib.bff_last_error()
+    assert lib.bff_cross_popcount_dev(p, 1, p, 2, 10, p, p, 0, 3, None) == -1 and b"bad sizes" in lib.bff_last_error()
+    assert lib.bff_cross_popcount_dev(p, 1, p, 2, 10, p, None, 0, 2, None) == -1 and b"null pointer" in lib.bff_last_error()
+    assert lib.bff_or_reduce_grouped(p, 10, 5, p, 256, p, p, p, p, p, 0, None, None, None) == -1
+    assert b"conf and conf_mean" in lib.bff_last_error()
+    assert lib.bff_or_reduce_grouped(p, 10, 5, p, 256, p, p, p, p, p, 2, p, None, None) == -1
+    assert lib.bff_or_reduce_grouped(p, 10, 5, p, 256, p, p, p, None, None, 0, None, None, None) == -1
+    assert lib.bff_or_reduce_grouped(p, 10, 5, p, 0, p, p, p, p, None, 0, None, None, None) == -1
+    assert lib.bff_group_components(p, None, p, 10, 0.5, 1, 0, p, 1, p, p, p, p, p, p, None) == -1
+    assert lib.bff_group_components(p, None, p, 10, 0.5, 1, 256, p, 1, None, p, p, p, p, p, None) == -1
+    assert lib.bff_group_components(None, None, p, 10, 0.5, 1, 256, p, 1, p, p, p, p, p, p, None) == -1
+    assert lib.bff_group_components(p, None, p, -1, 0.5, 1, 256, p, 1, p, p, p, p, p, p, None) == -1
+    assert lib.bff_resolve_overlaps_dev(p, 0, 10, p, None, p, p, p, None) == -1
+    assert lib.bff_resolve_overlaps_dev(p, 256, 10, p, None, p, p, None, None) == -1
+    assert lib.bff_clear_flagged_chunks_unless(p, 1, 10, p, None, None) == -1
+    assert lib.bff_clear_flagged_chunks_unless(p, -1, 10, p, p, None) == -1
 
 
 def test_size_limits_are_rejected_on_the_host():
@@ -57,6 +77,10 @@ def test_size_limits_are_rejected_on_the_host():
     assert lib.bff_rle_to_labels(p, p, p, p, 1, 100, 32, None, p, None, None) == -1
     assert lib.bff_project_views(p, 10, 1024, p, p, 1, p, p, 65536, 65536, 0.08, None, None, None, 32, None, None, None, p,
                                  None, 0, 1, None, None, None, None, None) == -2 and b"2^31 pixels" in lib.bff_last_error()
+    # groups formed on the device: capacity beyond BFF_GROUP_CAP_MAX, overlap capacity beyond the one-pass resolution
+    assert lib.bff_group_components(p, None, p, 10, 0.5, 1, 513, p, 1, p, p, p, p, p, p, None) == -2
+    assert b"512 groups" in lib.bff_last_error()
+    assert lib.bff_resolve_overlaps_dev(p, 4097, 10, p, None, p, p, p, None) == -2 and b"4096 rows" in lib.bff_last_error()
 
 
 def test_no_cpu_fallback():
@@ -123,6 +147,49 @@ def test_groups_from_labels_matches_closure_components():
     a = np.array([[1, 1, 0], [1, 0, 0], [0, 0, 0]], bool)
     assert pref.connected_groups(torch.from_numpy(a).float()) == [[0, 1], []]
     assert groups_from_labels(np.array([0, 0, 2]), np.array([True, False, False])) == [[0, 1], []]
+
+
+@pytest.mark.parametrize("tree", ["chain", "random"])
+def test_group_tables_reference_matches_component_csr(tree):
+    """The NumPy reference of bff_group_components' tables (tests/group_tables_ref.py) == projection.component_csr and
+    the native host twin, and for min_members >= 1 == groups_from_labels, on random forests."""
+    from beyond_fixed_forms_amd import _lib
+    from beyond_fixed_forms_amd.projection import component_csr, groups_from_labels
+    from group_tables_ref import build_components, group_tables_ref
+    rng = np.random.default_rng(3 if tree == "chain" else 4)
+    for trial in range(40):
+        n = int(rng.integers(1, 3000))
+        thr = float(rng.choice([0.5, 1.0, 1.5, -1.0]))
+        mm = int(rng.choice([-1, 0, 1, 2, 5]))
+        cap = int(rng.choice([1, 7, 256, 512]))
+        big = [s for s in (31, 32, 33, 64, 65, 1100) if rng.random() < 0.4]
+        alive = int(rng.integers(0, 20))
+        room = n - sum(big) - alive
+        if room < 0:
+            big, alive, room = [], 0, n
+        fixed = sum(s >= max(mm, 1) for s in big) + (alive if (1 > thr and max(mm, 1) <= 1) else 0)
+        k_goal = fixed + int(rng.integers(0, room // (max(mm, 2) + 2) + 1))
+        parent, comp, area = build_components(rng, n, k_goal, big, thr, mm, alive, tree)
+        assert (parent <= np.arange(n)).all() and (comp[parent] == comp).all() and (comp[comp] == comp).all()
+        ref = group_tables_ref(comp, area, thr, mm, cap)
+        assert ref["K"] == k_goal
+        loops = (area > 0) & bool(np.float32(1) > np.float32(thr))
+        offs, members, sizes, n_void = component_csr(comp, loops, mm)
+        k = min(ref["K"], cap)
+        assert sizes.size == ref["K"] and np.array_equal(sizes[:k], ref["sizes"])
+        assert np.array_equal(offs[:k + 1], ref["offs"]) and np.array_equal(members[:offs[k]], ref["members"])
+        assert np.array_equal(members[offs[:-1]][:k], ref["first"])
+        assert ref["info"][2] == (sizes.max() if sizes.size else 0)
+        assert ref["info"][1] == (1 if sizes.size > cap else 0) | (2 if n_void else 0)
+        assert ref["info"][3] == ref["slices"].shape[0] == sum(-(-int(s) // 32) for s in sizes[:k])
+        if ref["slices"].size:
+            g, lo, hi = ref["slices"].T
+            assert np.array_equal(np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)]), np.arange(offs[k]))
+            assert ((hi - lo) <= 32).all() and (offs[g] <= lo).all() and (hi <= offs[g + 1]).all()
+        o2, m2, s2, v2 = _lib.host_component_csr(comp, loops, mm)
+        assert np.array_equal(o2, offs) and np.array_equal(m2, members) and np.array_equal(s2, sizes) and v2 == n_void
+        if mm >= 1:
+            assert groups_from_labels(comp, loops, mm) == [members[offs[g]:offs[g + 1]].tolist() for g in range(sizes.size)]
 
 
 def test_prepare_scene_frame_table_cpu():
