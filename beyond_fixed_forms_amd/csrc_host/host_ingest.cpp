@@ -124,6 +124,10 @@ long long bff_host_pack_rles(PyObject *rles, int32_t *run_start, int32_t *run_en
 // frames: sequence of C-contiguous buffers of exactly `bytes_each` bytes (e.g. the uint16 depth frames of a scene);
 // copies frame i to dst + i * bytes_each on n_threads threads with the GIL released.  Returns the number of frames
 // or -1 (bad object / size).
+// Aliasing contract: the sources must not live in the destination.  If any frame overlaps [dst, dst + n * bytes_each)
+// -- even one that already lies in its own slot -- the call DECLINES with -1 before a single byte is written, so the
+// frames are still intact and the caller packs into other memory.  (Copying in place cannot be made right by ordering
+// the copies: a permutation of frames inside their own block has cycles, and the copies run on several threads.)
 long long bff_host_pack_frames(PyObject *frames, void *dst, long long bytes_each, int n_threads)
 {
     PyObject *seq = PySequence_Fast(frames, "frames must be a sequence");
@@ -137,6 +141,13 @@ long long bff_host_pack_frames(PyObject *frames, void *dst, long long bytes_each
             PyErr_Clear(); rc = -1; break;
         }
         if (views[(size_t)got].len != bytes_each) { rc = -1; ++got; break; }
+    }
+    if (rc >= 0 && bytes_each > 0) {
+        const uintptr_t d_lo = reinterpret_cast<uintptr_t>(dst), d_hi = d_lo + (uintptr_t)n * (uintptr_t)bytes_each;
+        for (Py_ssize_t i = 0; i < n; ++i) {
+            const uintptr_t s_lo = reinterpret_cast<uintptr_t>(views[(size_t)i].buf);
+            if (s_lo < d_hi && s_lo + (uintptr_t)bytes_each > d_lo) { rc = -1; break; }
+        }
     }
     if (rc >= 0) {
         Py_BEGIN_ALLOW_THREADS

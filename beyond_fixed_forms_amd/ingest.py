@@ -13,6 +13,7 @@ overlaps the uploads of scene i+1 with the kernels of scene i (`Ingestor`).  Inp
 from __future__ import annotations
 
 import ctypes
+import inspect
 import os
 import threading
 import time
@@ -309,7 +310,11 @@ def _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads):
             if torch.is_tensor(held) and held.is_pinned() and held.numel() * held.element_size() >= each * len(frames):
                 flat = held.view(-1).view(torch.uint8)[:each * len(frames)]
         if flat is None:
-            stage = staging.get("depth", each * len(frames))
+            # never pack into memory the sources live in: frames that io.load_scene(staging=...) decoded into this
+            # loader's "depth" buffer in another order than the upload's (a mask_2d entry without masks gets a later
+            # slot or none) are packed into a second pinned buffer; bff_host_pack_frames declines aliasing on its own
+            key = "depth.packed" if _frames_inside(frames, staging.buf.get("depth")) else "depth"
+            stage = staging.get(key, each * len(frames))
             if host_lib().bff_host_pack_frames(frames, stage.data_ptr(), each, n_threads) != len(frames):
                 return None
             flat = stage[:each * len(frames)]
@@ -331,6 +336,19 @@ def _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads):
     else:
         depth_dev = torch.zeros((0, h * w), dtype=torch.float32, device=dev)
     return depth_dev, raw_keep, raw_size
+
+
+def _frames_inside(frames, held):
+    """Does any of the host arrays `frames` lie (partly) inside the buffer `held` (a staging tensor or None)?"""
+    if held is None:
+        return False
+    lo = held.data_ptr()
+    hi = lo + held.numel() * held.element_size()
+    for f in frames:
+        a = f.__array_interface__["data"][0]
+        if a < hi and a + f.nbytes > lo:
+            return True
+    return False
 
 
 def _cloud_to_device(pts, n, stride, n_pad, dev, staging):
@@ -495,6 +513,19 @@ def prepare_stage1_fast(stage1: dict, device, staging: Staging, n_threads=2):
     return DeviceStage1(n_points, rs, re, offs, [idx_to_label(int(i)) for i in stage1["final_class"]])
 
 
+def _takes_staging(loader) -> bool:
+    """Does the loader accept a `staging` keyword?  Decided from its signature (functools.partial objects are looked
+    through), never by calling it and catching TypeError: a TypeError raised inside the loader is the caller's to see."""
+    try:
+        params = inspect.signature(loader).parameters
+    except (TypeError, ValueError):                   # no introspectable signature: called without
+        return False
+    p = params.get("staging")
+    if p is not None:
+        return p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY)
+    return any(q.kind == q.VAR_KEYWORD for q in params.values())
+
+
 class Ingestor:
     """Loader threads, each with its own HIP stream and pinned staging: `submit(scene)` returns a future of
     (DeviceScene, DeviceStage1 | None, ready event).  The consumer makes its compute stream wait for the event
@@ -520,10 +551,8 @@ class Ingestor:
             tl.stream = torch.cuda.Stream(device=self.device)
             tl.staging = Staging()
         if callable(scene):                           # a loader (e.g. io.load_scene of one scene): file reads run here too
-            try:                                      # loaders that take `staging` decode depth straight into pinned memory
-                scene = scene(staging=tl.staging)
-            except TypeError:
-                scene = scene()
+            # loaders that take `staging` decode depth straight into pinned memory
+            scene = scene(staging=tl.staging) if _takes_staging(scene) else scene()
         with torch.cuda.stream(tl.stream):
             ds = prepare_scene_fast(scene, self.cfg, self.device, self.with_viewed, tl.staging, self.native_threads)
             st1 = None
@@ -545,10 +574,7 @@ class Ingestor:
             tl.stream = torch.cuda.Stream(device=self.device)
             tl.staging = Staging()
         if callable(item):                            # e.g. io.load_scene_classes of one scene
-            try:
-                item = item(staging=tl.staging)
-            except TypeError:
-                item = item()
+            item = item(staging=tl.staging) if _takes_staging(item) else item()
         masks = [item.masks[c] for c in classes]
         if not hasattr(tl, "class_staging"):
             tl.class_staging = Staging()              # the classes' small tables do not wait for the scene's depth copy

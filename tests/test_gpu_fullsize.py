@@ -1,7 +1,9 @@
 """GPU parity at BASELINE config 2's full size (200k points, 300 views @968x1296, 30 masks/view,
 Ins = 9000) through size-independent properties, plus the oracle on a frame subset at full N / HxW / M.
-The complete oracle run at this size (~40 s of CPU on 16 threads) is part of the suite; set
-BFF_SKIP_FULL_SCALE=1 to leave it out."""
+The complete oracle run at this size (~40 s of CPU on 16 threads) is part of the suite, and so are two more on the
+scenes and the depth format the benchmark times (test_timed_configuration_against_the_complete_oracle: 41 s for the
+"default" and 41 s for the "many" variant on 16 threads, measured next to an MI355X); set BFF_SKIP_FULL_SCALE=1 to
+leave all three out."""
 import copy
 import os
 import warnings
@@ -167,3 +169,87 @@ def test_complete_oracle_at_config2(c2):
     fexp = rref.refine_class_ref([(scene.scene_id, scene.stage1, exp)], cfg, "table", enc)
     fd = fin[scene.scene_id].to_dict()
     assert torch.equal(fd["ins"].cpu(), fexp[scene.scene_id]["ins"]) and torch.equal(fd["conf"], fexp[scene.scene_id]["conf"])
+
+
+# The scenes bench.py rotates through its timed loop ("default" / "many" of its SCENE_VARIANTS; seeds as its first
+# rank's first two scenes): the generator's default, and 40 smaller objects with one exact full-silhouette mask per
+# visible object and view, where many stage-2 instances survive the filters (K >> 1 through the back half).
+TIMED_VARIANTS = {
+    "default": dict(seed=0),
+    "many": dict(seed=1, cut_masks=False, n_objects=40, distinct_masks=True, dilate=False),
+}
+_timed = {}
+
+
+def timed_run(variant):
+    """One variant in the timed configuration -- 16-bit depth at the sensor's resolution (with_sensor_depth), ingested by
+    prepare_scene_fast, projected by the one-call path -- next to the oracle on the host restatement of the resize.
+    Computed once per module run: the joint refinement needs both variants."""
+    if variant not in _timed:
+        import time
+        from beyond_fixed_forms_amd import _lib
+        from beyond_fixed_forms_amd.config import Config
+        from beyond_fixed_forms_amd.ingest import prepare_scene_fast
+        from beyond_fixed_forms_amd.io import resize_bilinear_f32
+        from beyond_fixed_forms_amd.projection import projection_back, projection_front
+        from beyond_fixed_forms_amd.synthetic import make_scene, with_sensor_depth
+        _lib.load()
+        scene = make_scene("c2", device=DEV, **TIMED_VARIANTS[variant])
+        scene.scene_id = f"scene_{variant}"
+        cfg = Config.with_defaults(width_2d=scene.width, height_2d=scene.height)
+        raw = with_sensor_depth(scene)
+        host = copy.copy(scene)               # what the reference holds after cv2.imread / 1000 + cv2.resize (restated)
+        host.depths = {f: resize_bilinear_f32(m.astype(np.float32) / np.float32(1000), scene.width, scene.height)
+                       for f, m in raw.depths_raw.items()}
+        torch.set_num_threads(16)
+        t0 = time.perf_counter()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            exp, dbg = pref.project_scene_ref(host, cfg, return_debug=True)
+        print(f"oracle on the {variant} variant: {time.perf_counter() - t0:.1f} s, {len(dbg['groups'])} groups, "
+              f"{len(exp['conf'])} stage-2 instances")
+        res = projection_back(projection_front(prepare_scene_fast(raw, cfg, DEV), cfg))
+        _timed[variant] = (scene, cfg, exp, dbg, res)
+    return _timed[variant]
+
+
+def timed_refinement():
+    """Both variants' results refined TOGETHER, as one class (a batch of two scenes, as the bench batches eight): the
+    similarity percentile of R:324 is taken over the class, so neither scene's final masks can be checked alone."""
+    if "final" not in _timed:
+        from beyond_fixed_forms_amd.refinement import TextSimilarity, refine_class
+        from beyond_fixed_forms_amd.synthetic import make_text_bank
+        from oracle.make_golden_shared import bank_encoder
+        runs = [timed_run(v) for v in TIMED_VARIANTS]
+        cfg = runs[0][1]
+        bank, index = make_text_bank(768, seed=0)
+        enc = bank_encoder(bank.float(), index)
+        fin = refine_class([(sc.scene_id, sc.stage1, res) for sc, _c, _e, _d, res in runs], cfg, "table", TextSimilarity(enc, DEV), DEV)
+        fexp = rref.refine_class_ref([(sc.scene_id, sc.stage1, exp) for sc, _c, exp, _d, _r in runs], cfg, "table", enc)
+        _timed["final"] = (fin, fexp)
+    return _timed["final"]
+
+
+@pytest.mark.skipif(os.environ.get("BFF_SKIP_FULL_SCALE") == "1", reason="two complete oracle runs at config 2; skipped on request")
+@pytest.mark.parametrize("variant", list(TIMED_VARIANTS))
+def test_timed_configuration_against_the_complete_oracle(variant):
+    """The configuration the headline number is printed on -- config 2, depth as 16-bit half-resolution frames resized
+    per point inside the sweep, prepare_scene_fast, the one-call path -- on both scene variants of the benchmark against
+    the complete oracle: groups, stage-2 masks, confidences and labels bit-identical, and the final masks of both scenes
+    refined as one class equal refine_class_ref's.
+    "many" is there for K >> 1: the oracle returns 3 stage-2 instances on "default" and 25 on "many" (of 40 objects)."""
+    scene, cfg, exp, dbg, res = timed_run(variant)
+    assert res.debug["path"] == "fast"                    # otherwise this checks another path than the timed one
+    assert list(res.groups) == dbg["groups"]
+    got = res.to_dict()
+    assert tuple(got["ins"].shape) == tuple(exp["ins"].shape) and torch.equal(got["ins"].cpu(), exp["ins"])
+    assert torch.equal(got["conf"].cpu(), exp["conf"]) and got["final_class"] == exp["final_class"]
+    k_default, k_many = (len(timed_run(v)[2]["conf"]) for v in ("default", "many"))
+    # a condition on the input, not a measurement: "many" must put many instances through the back half -- at least half
+    # of its 40 objects, and several times what the default scene leaves
+    assert k_default >= 1 and k_many >= 20 and k_many >= 5 * k_default, (k_default, k_many)
+    fin, fexp = timed_refinement()
+    fd, fe = fin[scene.scene_id].to_dict(), fexp[scene.scene_id]
+    assert not isinstance(fe["ins"], list) and fe["ins"].shape[0] >= 1
+    assert tuple(fd["ins"].shape) == tuple(fe["ins"].shape) and torch.equal(fd["ins"].cpu(), fe["ins"])
+    assert torch.equal(fd["conf"].cpu(), fe["conf"].cpu()) and list(fd["final_class"]) == list(fe["final_class"])

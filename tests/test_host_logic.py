@@ -449,3 +449,98 @@ def test_native_png_decoder_declines_what_it_does_not_cover(tmp_path):
     out = np.zeros((2, 20, 31), np.uint16)
     n = host_lib().bff_host_decode_depth_pngs([str(ok), str(cut)], out.ctypes.data, 20, 31, status.ctypes.data, 2)
     assert n == 1 and status[0] == 0 and status[1] != 0 and np.array_equal(out[0], img) and not out[1].any()
+
+
+PACK_ORDERS = {
+    # new order of the frames of a block, given the old one: the two orders io.load_scene's staged block and
+    # prepare_scene_fast's slots differ by when a mask_2d entry has no masks, and the worst permutation
+    "moved_back": lambda n: [0] + list(range(2, n)) + [1],        # detection-ratio mode: frame 1 gets a later slot
+    "dropped": lambda n: [0] + list(range(2, n)),                 # occurrence mode: frame 1 gets no slot
+    "reversed": lambda n: list(range(n))[::-1],
+}
+
+
+@pytest.mark.parametrize("threads", [1, 2, 4])
+@pytest.mark.parametrize("order", list(PACK_ORDERS))
+def test_pack_frames_with_sources_inside_the_destination(order, threads):
+    """bff_host_pack_frames called with frames that are views of its own destination, in another order (what
+    ingest._depth_to_device did with a block io.load_scene(staging=...) had decoded in its own order).  Contract
+    (pinned above the function in host_ingest.cpp): it DECLINES with -1 and leaves every frame as it was.  The exact
+    reordered block would be the only other acceptable outcome; anything else is silent corruption of depth."""
+    from beyond_fixed_forms_amd import ingest
+    n, h, w = 60, 24, 32                                          # 15 frames per thread at 4 threads
+    rng = np.random.default_rng(17)
+    frames = rng.integers(0, 65536, (n, h, w)).astype(np.uint16)
+    block = frames.copy()
+    new = PACK_ORDERS[order](n)
+    views = [block[k] for k in new]
+    got = ingest.host_lib().bff_host_pack_frames(views, block.ctypes.data, h * w * 2, threads)
+    if got == -1:
+        assert np.array_equal(block, frames)                      # declined: nothing was written
+    else:
+        assert got == len(new) and np.array_equal(block[:len(new)], frames[new])
+    assert got == -1                                              # the contract chosen: aliasing is declined
+    # a single frame already in its own slot, and a source that overlaps the destination by one byte: declined too
+    assert ingest.host_lib().bff_host_pack_frames([block[0]], block.ctypes.data, h * w * 2, threads) == -1
+    flat = block.reshape(-1).view(np.uint8)
+    tail = flat[h * w * 2 - 1:2 * h * w * 2 - 1]
+    assert ingest.host_lib().bff_host_pack_frames([tail], flat.ctypes.data, h * w * 2, threads) == -1
+    assert np.array_equal(block, frames)
+
+
+@pytest.mark.parametrize("threads", [1, 2, 4])
+def test_pack_frames_disjoint_sources_give_the_exact_block(threads):
+    """The common case: sources outside the destination, any order, also directly next to it on either side."""
+    from beyond_fixed_forms_amd import ingest
+    n, h, w = 60, 24, 32
+    rng = np.random.default_rng(18)
+    frames = rng.integers(0, 65536, (n, h, w)).astype(np.uint16)
+    for order in PACK_ORDERS.values():
+        new = order(n)
+        dst = np.full((n, h, w), 0xABCD, np.uint16)
+        assert ingest.host_lib().bff_host_pack_frames([frames[k] for k in new], dst.ctypes.data, h * w * 2, threads) == len(new)
+        assert np.array_equal(dst[:len(new)], frames[new]) and np.all(dst[len(new):] == 0xABCD)
+    # one allocation: [frame before | destination of 3 frames | frame after] -- touching, not overlapping
+    arena = rng.integers(0, 65536, (5, h, w)).astype(np.uint16)
+    keep = arena.copy()
+    srcs = [arena[0], arena[4], arena[0]]
+    assert ingest.host_lib().bff_host_pack_frames(srcs, arena[1:].ctypes.data, h * w * 2, threads) == 3
+    assert np.array_equal(arena[1:4], np.stack([keep[0], keep[4], keep[0]]))
+    assert np.array_equal(arena[0], keep[0]) and np.array_equal(arena[4], keep[4])
+    assert ingest.host_lib().bff_host_pack_frames([], arena.ctypes.data, h * w * 2, threads) == 0
+
+
+def test_repack_key_and_loader_signature_rules():
+    """Host-side rules of the ingestion: (a) frames that lie inside the loader's "depth" staging buffer are recognised
+    (they are then packed into a second buffer, never into their own); (b) whether a loader is given `staging` is read
+    from its signature, through functools.partial, not found out by calling it."""
+    import functools
+    from beyond_fixed_forms_amd import ingest, io as bio
+    held = torch.empty(4 * 24 * 2, dtype=torch.uint8)
+    inside = held.numpy().view(np.uint16).reshape(4, 24)
+    other = np.zeros((4, 24), np.uint16)
+    assert ingest._frames_inside([inside[2]], held) and ingest._frames_inside([other[0], inside[3]], held)
+    assert not ingest._frames_inside([other[0], other[3]], held) and not ingest._frames_inside([inside[0]], None)
+    assert not ingest._frames_inside([], held)
+    bigger = torch.empty(6 * 48, dtype=torch.uint8)               # a view that ends where the buffer begins / begins where it ends
+    mid = bigger[48:5 * 48]
+    assert not ingest._frames_inside([bigger.numpy()[:48], bigger.numpy()[5 * 48:]], mid)
+    assert ingest._frames_inside([bigger.numpy()[1:49]], mid) and ingest._frames_inside([bigger.numpy()[5 * 48 - 1:]], mid)
+
+    def plain():
+        return None
+
+    def keyword_only(*, staging=None):
+        return None
+
+    def anything(**kw):
+        return None
+
+    def positional_only(staging, /):
+        return None
+
+    assert ingest._takes_staging(functools.partial(bio.load_scene, {}, "table", "scene0000_00", depth_on_device=True))
+    assert ingest._takes_staging(functools.partial(bio.load_scene_classes, {}, ["table"], "scene0000_00"))
+    assert ingest._takes_staging(keyword_only) and ingest._takes_staging(anything)
+    assert not ingest._takes_staging(plain) and not ingest._takes_staging(lambda: None)
+    assert not ingest._takes_staging(functools.partial(lambda a: a, 1)) and not ingest._takes_staging(positional_only)
