@@ -9,6 +9,12 @@ call (np.linalg.inv over the stack = the same gesv per matrix as P:425), and the
 device (bff_cloud_layout).  Everything is enqueued on the caller's stream, so a loader thread with its own stream
 overlaps the uploads of scene i+1 with the kernels of scene i (`Ingestor`).  Inputs the fast path does not cover
 (unsorted / overlapping runs, mixed frame sizes, CPU devices) fall back to scene.prepare_scene: same results.
+
+The bookkeeping is scene.py's (frame_table, label_ids, raw_depth_on_device, device_scene); this module adds the
+transport: _run_tables, _gather_confidences and _upload_tables for one mask list (_class_to_device), _depth_to_device
+and _cloud_to_device for the scene (_geometry_to_device).  prepare_scene_fast is the two halves on one Staging between
+one wait and one fence; prepare_geometry_fast and prepare_class_fast are one half each, with a wait and a fence of
+their own.
 """
 from __future__ import annotations
 
@@ -24,8 +30,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .scene import (DeviceScene, SceneGeometry, class_frame_table, class_word_bits, count_geometry_viewed, frame_union,
-                    keep_raw_depth, prepare_class, prepare_geometry, prepare_scene, tile_raw_depth, viewed_frame_ids)
+from .scene import (DeviceScene, SceneGeometry, class_inv_poses, class_word_bits, concat_confidences, confidence_dtype,
+                    count_geometry_viewed, device_scene, frame_table, frame_union, label_ids, new_geometry, padded_points,
+                    prepare_class, prepare_geometry, prepare_scene, raw_depth_on_device, slots_on_first_use,
+                    viewed_frame_ids, with_viewed_counts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libbff_host.so")
@@ -122,220 +130,151 @@ def pack_rles(rles, expect_length, staging: Staging, tag, n_threads=4):
     return rs[:got], re[:got], offs[:n + 1]
 
 
-def prepare_scene_fast(scene, cfg, device="cuda", with_viewed=True, staging: Staging = None, n_threads=4) -> DeviceScene:
-    """scene.prepare_scene with the byte work native / on the device; everything is enqueued on the current stream."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        return prepare_scene(scene, cfg, device=device, with_viewed=with_viewed)
-    staging = staging or Staging()
-    lap = _Lap()
-    staging.wait()                                   # the previous scene's copies out of these buffers are done
-    lap("wait for the staging buffers")
+def _run_tables(rles, h, w, staging, dev, n_threads):
+    """2-D RLE -> (run_start, run_end, mask_run_offs) on the device: built by native threads straight into pinned
+    staging.  None when pack_rles declines (the caller takes the exact slow path)."""
+    if rles:
+        packed = pack_rles(rles, h * w, staging, "m2d", n_threads)
+        if packed is None:
+            return None
+    else:
+        z = torch.zeros(0, dtype=torch.int32)
+        packed = (z, z, torch.zeros(1, dtype=torch.int32))
+    return [torch.as_tensor(t).to(dev, non_blocking=True) for t in packed]
+
+
+def _gather_confidences(conf_list, staging, dev):
+    """The frames' confidences as one device tensor.  Host tensors (the mask_2d file's) are gathered into the pinned
+    staging by ONE native call: torch.cat / reshape / numpy() per frame are ATen calls, each of which hands the GIL over
+    and back; with the loader threads and the compute thread contending that cost 30-60 us per call, 8-18 ms per scene
+    (BFF_INGEST_TRACE).  Tensors already on a GPU stay there (no round trip through the host, which would wait for this
+    stream's uploads)."""
+    if not (conf_list and all(c.device.type == "cpu" and c.is_contiguous() for c in conf_list)):
+        return concat_confidences(conf_list, on_host=False).to(dev)
+    dtype = confidence_dtype(conf_list)
+    meta = np.empty((2, len(conf_list)), dtype=np.int64)
+    meta[0] = [c.data_ptr() for c in conf_list]
+    meta[1] = [c.numel() * conf_list[0].element_size() for c in conf_list]
+    total = int(meta[1].sum())
+    cstage = staging.get("conf", total)
+    if host_lib().bff_host_gather_bytes(meta[0].ctypes.data, meta[1].ctypes.data, len(conf_list), cstage.data_ptr()) != total:
+        raise ValueError("confidence tensors could not be gathered")
+    return cstage[:total].view(dtype).to(dev, non_blocking=True)
+
+
+def _upload_tables(tables, inv, staging, dev):
+    """int32 host tables + the float64 inverse poses [F][16] through ONE pinned block and one copy
+    -> (the tables as device views, inv_pose)."""
+    sizes = [t.size for t in tables]
+    n_int = 4 * sum(sizes)
+    at = (n_int + 7) // 8 * 8
+    tstage = staging.get("tables", at + 8 * inv.size + 64).numpy()
+    np.concatenate(tables, out=tstage[:n_int].view(np.int32))
+    tstage[at:at + 8 * inv.size].view(np.float64)[:] = inv.reshape(-1)
+    tdev = staging.buf["tables"][:at + 8 * inv.size].to(dev, non_blocking=True)
+    tint = tdev[:n_int].view(torch.int32)
+    cuts = np.cumsum([0] + sizes)
+    return [tint[cuts[k]:cuts[k + 1]] for k in range(len(tables))], \
+        tdev[at:at + 8 * inv.size].view(torch.float64).view(inv.shape[0], 16)
+
+
+def _geometry_to_device(scene, cfg, ids, n_viewed, dev, staging, n_threads, lap=lambda phase: None):
+    """scene._geometry through pinned staging (no wait, no fence: the callers' business): poses inverted in one batched
+    call (np.linalg.inv over a stack = the per-matrix LAPACK call of P:425), the frames `ids` in one copy, the cloud
+    laid out on the device.  None when the depth frames are of mixed sizes / dtypes (exact slow path)."""
     h, w = int(cfg.height_2d), int(cfg.width_2d)
     pts = np.asarray(scene.points)
     if pts.dtype != np.float64 or pts.ndim != 2 or pts.shape[1] < 3 or not pts.flags.c_contiguous:
         pts = np.ascontiguousarray(pts[:, :3], dtype=np.float64)
-    n, stride = pts.shape
-    nw = (n + 63) // 64
-    n_pad = max(1024, ((n + 1023) // 1024) * 1024)
-    nb = lambda x: torch.as_tensor(x).to(dev, non_blocking=True)
-
-    # ---- frame table (same bookkeeping as prepare_scene)
-    mask_2d = scene.mask_2d
-    max_m = max((len(fr["segmented_frame_masks"]) for fr in mask_2d), default=0)
-    word_bits = 32 if max_m <= 32 else 64
-    viewed = _viewed_ids_cached(scene, cfg.downsample_ratio) if with_viewed else []
-    viewed_left = dict.fromkeys(viewed)
-    depth_slot, depth_ids = {}, []
-
-    def slot(fid):
-        s = depth_slot.get(fid)
-        if s is None:
-            s = depth_slot[fid] = len(depth_ids)
-            depth_ids.append(fid)
-        return s
-
-    pose_ids, d_idx, f_mask, f_rowbase, f_nmask, f_flags = [], [], [], [], [], []
-    all_rles, view_mask_offs, conf_list, labels = [], [0], [], []
-    row = 0
-    for fr in mask_2d:
-        fid = fr["frame_id"][:-4]
-        rles = fr["segmented_frame_masks"]
-        m = len(rles)
-        if not (len(fr["confidences"]) == m and len(fr["labels"]) == m):
-            raise ValueError(f"frame {fid}: masks / confidences / labels differ in length")
-        first = True
-        for c0 in range(0, m, word_bits):
-            mc = min(word_bits, m - c0)
-            pose_ids.append(fid); d_idx.append(slot(fid))
-            f_mask.append(len(view_mask_offs) - 1); f_rowbase.append(row); f_nmask.append(mc)
-            counted = first and fid in viewed_left
-            if counted:
-                del viewed_left[fid]
-            f_flags.append(1 if counted else 0)
-            first = False
-            view_mask_offs.append(view_mask_offs[-1] + mc)
-            row += mc
-        all_rles += rles
-        conf_list.append(fr["confidences"])
-        labels += fr["labels"]
-    n_mask_frames = len(pose_ids)
-    for fid in viewed_left:
-        pose_ids.append(fid); d_idx.append(slot(fid)); f_mask.append(-1); f_rowbase.append(0); f_nmask.append(0); f_flags.append(1)
-    nf = len(pose_ids)
-
-    lap("frame table (python)")
-    # ---- 2-D RLE -> run tables (native threads), straight into pinned staging
-    packed = pack_rles(all_rles, h * w, staging, "m2d", n_threads) if all_rles else None
-    lap("run tables (native)")
-    if all_rles and packed is None:
-        return prepare_scene(scene, cfg, device=device, with_viewed=with_viewed)       # rare inputs: exact slow path
-    if packed is None:
-        z = torch.zeros(0, dtype=torch.int32)
-        packed = (z, z, torch.zeros(1, dtype=torch.int32))
-    run_start, run_end, run_offs = (nb(t) for t in packed)
-
-    # ---- poses: one batched inverse (np.linalg.inv over a stack = the per-matrix LAPACK call of P:425)
-    poses = scene.poses
-    if nf:
-        uniq = list(dict.fromkeys(pose_ids))
-        inv_u = np.linalg.inv(np.stack([np.asarray(poses[f], dtype=np.float64) for f in uniq]))
-        lut = {f: k for k, f in enumerate(uniq)}
-        inv = inv_u[[lut[f] for f in pose_ids]].reshape(nf, 16)
-    else:
-        inv = np.zeros((0, 16))
-
-    lap("run-table upload + pose inverses")
-    # ---- depth: frames packed into pinned staging by native threads, ONE asynchronous copy
-    got = _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads)
-    if got is None:
-        return prepare_scene(scene, cfg, device=device, with_viewed=with_viewed)       # mixed sizes / dtypes: slow path
-    depth_dev, raw_keep, raw_size = got
-
+    inv = np.linalg.inv(np.stack([np.asarray(scene.poses[f], dtype=np.float64) for f in ids])).reshape(len(ids), 16) \
+        if ids else np.zeros((0, 16))
+    lap("pose inverses")
+    depth3 = _depth_to_device(scene, ids, pts.shape[0], h, w, dev, staging, n_threads)
+    if depth3 is None:
+        return None
     lap("depth (pack / enqueue / tile)")
-    # ---- cloud: upload as stored, sort + lay out on the device
-    xyz, unsort, perm, sort, bounds = _cloud_to_device(pts, n, stride, n_pad, dev, staging)
-
+    xyz, unsort, perm, bounds = _cloud_to_device(pts, dev, staging)
     lap("cloud (copy to pinned, enqueue, layout)")
-    # ---- small tables: one pinned block, one copy
-    conf, conf_d = None, None
-    if conf_list:
-        dts = {c.dtype for c in conf_list}
-        if len(dts) != 1:
-            raise TypeError(f"mixed confidence dtypes {dts}")
-        if all(c.device.type == "cpu" and c.is_contiguous() for c in conf_list):
-            # host tensors (the mask_2d file's): gathered into the pinned staging by ONE native call.  torch.cat / reshape /
-            # numpy() per frame are ATen calls, each of which hands the GIL over and back: with the loader threads and the
-            # compute thread contending that cost 30-60 us per call, 8-18 ms per scene (BFF_INGEST_TRACE)
-            nf_c = len(conf_list)
-            esz = conf_list[0].element_size()
-            meta = np.empty((2, nf_c), dtype=np.int64)
-            meta[0] = [c.data_ptr() for c in conf_list]
-            meta[1] = [c.numel() * esz for c in conf_list]
-            total = int(meta[1].sum())
-            cstage = staging.get("conf", total)
-            if host_lib().bff_host_gather_bytes(meta[0].ctypes.data, meta[1].ctypes.data, nf_c, cstage.data_ptr()) != total:
-                raise ValueError("confidence tensors could not be gathered")
-            conf_d = cstage[:total].view(conf_list[0].dtype).to(dev, non_blocking=True)
-        else:
-            conf = torch.cat([c.reshape(-1) for c in conf_list])
-    else:
-        conf = torch.zeros(0, dtype=torch.float16)
+    return new_geometry(scene, h, w, pts.shape[0], ids, inv, n_viewed, xyz, depth3, bounds, unsort, perm)
+
+
+def _class_to_device(geom, ft, word_bits, runs, staging, shared, lap=lambda phase: None) -> DeviceScene:
+    """scene._class_tables through pinned staging (no wait, no fence): `runs` from _run_tables, the confidences in one
+    native gather, the frame table + label ids + inverse poses as one block."""
+    dev = geom.xyz.device
+    conf = _gather_confidences(ft.conf_list, staging, dev)
     lap("small tables: confidences")
-    ids = {s: k for k, s in enumerate(dict.fromkeys(labels))}       # distinct label strings in order of first appearance
-    if len(ids) <= 1:
-        label_id = np.zeros(len(labels), dtype=np.int32)
-    else:
-        label_id = np.fromiter(map(ids.__getitem__, labels), dtype=np.int32, count=len(labels))
+    label_id, n_ids = label_ids(ft.labels)
     lap("small tables: label ids")
-    tables = [np.asarray(a, dtype=np.int32) for a in (d_idx, f_mask, f_rowbase, f_nmask, f_flags, view_mask_offs)] + [label_id]
-    sizes = [t.size for t in tables]
-    tstage = staging.get("tables", 4 * sum(sizes) + 8 * inv.size + 64).numpy()
-    ti = tstage[:4 * sum(sizes)].view(np.int32)
-    np.concatenate(tables, out=ti)
-    at = (4 * sum(sizes) + 7) // 8 * 8
-    tstage[at:at + 8 * inv.size].view(np.float64)[:] = inv.reshape(-1)
-    lap("small tables: pack")
-    tdev = staging.buf["tables"][:at + 8 * inv.size].to(dev, non_blocking=True)
-    lap("small tables: enqueue")
-    tint = tdev[:4 * sum(sizes)].view(torch.int32)
-    cuts = np.cumsum([0] + sizes)
-    d_idx_d, f_mask_d, f_rowbase_d, f_nmask_d, f_flags_d, vmo_d, label_d = (tint[cuts[k]:cuts[k + 1]] for k in range(7))
-    inv_d = tdev[at:at + 8 * inv.size].view(torch.float64).view(nf, 16)
-    if conf_d is not None:
-        pass
-    elif conf.is_cuda:                               # already on a GPU (a caller that kept the detector's outputs there): no
-        conf_d = conf.to(dev)                        # round trip through the host, which would wait for this stream's uploads
-    elif conf.numel():                               # through the staging too: a pin_memory() per scene is a hipHostMalloc
-        cstage = staging.get("conf", conf.numel() * conf.element_size())
-        cview = cstage[:conf.numel() * conf.element_size()].view(conf.dtype)
-        cview.copy_(conf)
-        conf_d = cview.to(dev, non_blocking=True)
-    else:
-        conf_d = conf.to(dev)
-    lap("small tables: confidences to pinned + enqueue")
+    tables, inv_pose = _upload_tables(ft.int_tables() + [label_id], class_inv_poses(geom, ft), staging, dev)
+    lap("small tables: pack + enqueue")
+    return device_scene(geom, ft, word_bits, tables, inv_pose, runs, conf, n_ids, shared)
+
+
+def prepare_scene_fast(scene, cfg, device="cuda", with_viewed=True, staging: Staging = None, n_threads=4) -> DeviceScene:
+    """scene.prepare_scene with the byte work native / on the device; everything is enqueued on the current stream."""
+    dev = torch.device(device)
+    slow = lambda: prepare_scene(scene, cfg, device=device, with_viewed=with_viewed)
+    if dev.type != "cuda":
+        return slow()
+    staging = staging or Staging()
+    lap = _Lap()
+    staging.wait()                                   # the previous scene's copies out of these buffers are done
+    lap("wait for the staging buffers")
+    viewed = _viewed_ids_cached(scene, cfg.downsample_ratio) if with_viewed else []
+    word_bits = class_word_bits(scene.mask_2d)
+    slot, ids = slots_on_first_use()
+    ft = frame_table(scene.mask_2d, word_bits, slot, viewed)
+    lap("frame table (python)")
+    runs = _run_tables(ft.rles, int(cfg.height_2d), int(cfg.width_2d), staging, dev, n_threads)
+    lap("run tables (native) + upload")
+    if runs is None:
+        return slow()                                # rare inputs: exact slow path
+    geom = _geometry_to_device(scene, cfg, ids, len(viewed), dev, staging, n_threads, lap)
+    if geom is None:
+        return slow()                                # mixed sizes / dtypes
+    ds = _class_to_device(geom, ft, word_bits, runs, staging, False, lap)
     staging.fence()                                  # the pinned buffers may be rewritten once these copies are done
-    lap("small tables: fence")
-    return DeviceScene(
-        scene_id=scene.scene_id, n_points=n, nw=nw, height=h, width=w,
-        cam_intr=np.asarray(scene.cam_intr, dtype=np.float64)[:3, :3].copy(), xyz=xyz, tile_bounds=bounds, depth=depth_dev,
-        inv_pose=inv_d, depth_index=d_idx_d, frame_mask=f_mask_d, frame_rowbase=f_rowbase_d, frame_nmask=f_nmask_d,
-        frame_flags=f_flags_d, n_frames=nf, n_mask_frames=n_mask_frames, n_viewed=len(viewed), word_bits=word_bits,
-        n_rows=row, run_start=run_start, run_end=run_end, mask_run_offs=run_offs, view_mask_offs=vmo_d, conf=conf_d,
-        labels=labels, label_id=label_d, n_label_ids=max(1, len(ids)), stage1=getattr(scene, "stage1", None),
-        unsort=unsort[:n] if sort else None, perm=perm if sort else None, depth_raw=raw_keep, depth_size=raw_size)
+    lap("fence")
+    return ds
 
 
 def _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads):
-    """The frames `depth_ids` of a scene on the device, in that order (prepare_scene_fast's layout rules): packed into
-    pinned staging by native threads and uploaded as ONE asynchronous copy.  -> (depth, depth_raw, depth_size), or None
-    when the frames are of mixed sizes / dtypes (the caller takes the exact slow path)."""
-    raw_keep = raw_size = None
+    """The frames `depth_ids` of a scene on the device, in that order (scene.host_depth_to_device's layout rules): packed
+    into pinned staging by native threads and uploaded as ONE asynchronous copy.  -> (depth, depth_raw, depth_size), or
+    None when the frames are of mixed sizes / dtypes (the caller takes the exact slow path)."""
     raw_depth = getattr(scene, "depths_raw", None)
     src = raw_depth if raw_depth is not None else scene.depths
     frames = [src[f] for f in depth_ids]
-    if frames:
-        f0 = frames[0]
-        want_dtype = np.uint16 if raw_depth is not None else np.float32
-        if any(getattr(f, "dtype", None) != want_dtype or f.shape != f0.shape or not f.flags.c_contiguous for f in frames) or \
-                (raw_depth is None and f0.shape != (h, w)):
+    if not frames:
+        return torch.zeros((0, h * w), dtype=torch.float32, device=dev), None, None
+    f0 = frames[0]
+    want_dtype = np.uint16 if raw_depth is not None else np.float32
+    if any(getattr(f, "dtype", None) != want_dtype or f.shape != f0.shape or not f.flags.c_contiguous for f in frames) or \
+            (raw_depth is None and f0.shape != (h, w)):
+        return None
+    each = f0.nbytes
+    # the frames may already lie, in upload order, in page-locked memory: a decoder that wrote them there
+    # (io.load_scene(staging=...) -> this loader's "depth" buffer) or the caller's own pinned block
+    staged = getattr(scene, "depth_staged", None) if raw_depth is not None else None
+    flat = None
+    if staged is not None and list(staged[1]) == depth_ids:
+        held = staged[0].buf.get("depth") if isinstance(staged[0], Staging) else staged[0]
+        if torch.is_tensor(held) and held.is_pinned() and held.numel() * held.element_size() >= each * len(frames):
+            flat = held.view(-1).view(torch.uint8)[:each * len(frames)]
+    if flat is None:
+        # never pack into memory the sources live in: frames that io.load_scene(staging=...) decoded into this
+        # loader's "depth" buffer in another order than the upload's (a mask_2d entry without masks gets a later
+        # slot or none) are packed into a second pinned buffer; bff_host_pack_frames declines aliasing on its own
+        key = "depth.packed" if _frames_inside(frames, staging.buf.get("depth")) else "depth"
+        stage = staging.get(key, each * len(frames))
+        if host_lib().bff_host_pack_frames(frames, stage.data_ptr(), each, n_threads) != len(frames):
             return None
-        each = f0.nbytes
-        # the frames may already lie, in upload order, in page-locked memory: a decoder that wrote them there
-        # (io.load_scene(staging=...) -> this loader's "depth" buffer) or the caller's own pinned block
-        staged = getattr(scene, "depth_staged", None) if raw_depth is not None else None
-        flat = None
-        if staged is not None and list(staged[1]) == depth_ids:
-            held = staged[0].buf.get("depth") if isinstance(staged[0], Staging) else staged[0]
-            if torch.is_tensor(held) and held.is_pinned() and held.numel() * held.element_size() >= each * len(frames):
-                flat = held.view(-1).view(torch.uint8)[:each * len(frames)]
-        if flat is None:
-            # never pack into memory the sources live in: frames that io.load_scene(staging=...) decoded into this
-            # loader's "depth" buffer in another order than the upload's (a mask_2d entry without masks gets a later
-            # slot or none) are packed into a second pinned buffer; bff_host_pack_frames declines aliasing on its own
-            key = "depth.packed" if _frames_inside(frames, staging.buf.get("depth")) else "depth"
-            stage = staging.get(key, each * len(frames))
-            if host_lib().bff_host_pack_frames(frames, stage.data_ptr(), each, n_threads) != len(frames):
-                return None
-            flat = stage[:each * len(frames)]
-        if raw_depth is not None:
-            from .io import bilinear_taps
-            hs, ws_ = f0.shape
-            raw_dev = flat.view(torch.int16).view(len(frames), hs, ws_).to(dev, non_blocking=True)
-            if keep_raw_depth(n, h, w):              # resident at the sensor's resolution: the sweep resizes per point
-                depth_dev, raw_keep = None, raw_dev
-                if tile_raw_depth():
-                    raw_keep, raw_size = _lib.tile_depth(raw_dev, metres=tile_raw_depth() == "f32"), (hs, ws_)
-            else:
-                taps = None
-                if (hs, ws_) != (h, w):
-                    taps = _taps_cache(hs, ws_, h, w, dev)
-                depth_dev = _lib.depth_from_u16(raw_dev, h, w, taps)
-        else:
-            depth_dev = flat.view(torch.float32).view(len(frames), h * w).to(dev, non_blocking=True)
-    else:
-        depth_dev = torch.zeros((0, h * w), dtype=torch.float32, device=dev)
-    return depth_dev, raw_keep, raw_size
+        flat = stage[:each * len(frames)]
+    if raw_depth is None:
+        return flat.view(torch.float32).view(len(frames), h * w).to(dev, non_blocking=True), None, None
+    raw_dev = flat.view(torch.int16).view((len(frames),) + f0.shape).to(dev, non_blocking=True)
+    return raw_depth_on_device(raw_dev, n, h, w)
 
 
 def _frames_inside(frames, held):
@@ -351,30 +290,29 @@ def _frames_inside(frames, held):
     return False
 
 
-def _cloud_to_device(pts, n, stride, n_pad, dev, staging):
-    """float64 [n][stride] cloud -> (xyz [3][n_pad] sorted along the Morton curve, unsort, perm, sorted?, tile bounds),
-    everything enqueued on the current stream (bff_cloud_layout)."""
+def _cloud_to_device(pts, dev, staging):
+    """float64 [n][stride] cloud -> (xyz [3][n_pad] sorted along the Morton curve, unsort, perm, tile bounds) as
+    scene.cloud_host_layout lays them out, everything enqueued on the current stream (bff_cloud_layout)."""
+    n, stride = pts.shape
+    n_pad = padded_points(n)
     pstage = staging.get("points", pts.nbytes)
     np.copyto(pstage.numpy()[:pts.nbytes].view(np.float64).reshape(n, stride), pts)
     pts_dev = pstage[:pts.nbytes].view(torch.float64).view(n, stride).to(dev, non_blocking=True)
     xyz = torch.empty((3, n_pad), dtype=torch.float64, device=dev)
-    unsort = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    if not n:
+        return xyz.zero_(), None, None, None
     sort = n > 1
-    perm = None
-    if n:
-        perm = torch.empty(n, dtype=torch.int32, device=dev)
-        codes = torch.empty(2 * n, dtype=torch.int32, device=dev)
-        box = torch.empty(6, dtype=torch.float64, device=dev)
-        need = ctypes.c_size_t(0)
-        _lib.call("bff_cloud_layout", None, n, stride, n_pad, 1, None, None, None, None, None, None, ctypes.byref(need))
-        temp = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev)
-        nbytes = ctypes.c_size_t(temp.numel())
-        _lib.call("bff_cloud_layout", _lib._ptr(pts_dev), n, stride, n_pad, 1 if sort else 0, _lib._ptr(xyz), _lib._ptr(unsort),
-                  _lib._ptr(perm), _lib._ptr(codes), _lib._ptr(box), _lib._ptr(temp), ctypes.byref(nbytes))
-    else:
-        xyz.zero_()
-    bounds = _lib.point_tile_bounds(xyz, n) if n else None
-    return xyz, unsort, perm, sort, bounds
+    unsort = torch.empty(n, dtype=torch.int32, device=dev)
+    perm = torch.empty(n, dtype=torch.int32, device=dev)
+    codes = torch.empty(2 * n, dtype=torch.int32, device=dev)
+    box = torch.empty(6, dtype=torch.float64, device=dev)
+    need = ctypes.c_size_t(0)
+    _lib.call("bff_cloud_layout", None, n, stride, n_pad, 1, None, None, None, None, None, None, ctypes.byref(need))
+    temp = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+    nbytes = ctypes.c_size_t(temp.numel())
+    _lib.call("bff_cloud_layout", _lib._ptr(pts_dev), n, stride, n_pad, 1 if sort else 0, _lib._ptr(xyz), _lib._ptr(unsort),
+              _lib._ptr(perm), _lib._ptr(codes), _lib._ptr(box), _lib._ptr(temp), ctypes.byref(nbytes))
+    return xyz, unsort if sort else None, perm if sort else None, _lib.point_tile_bounds(xyz, n)
 
 
 def prepare_geometry_fast(scene, cfg, mask_2ds, device="cuda", with_viewed=True, staging: Staging = None,
@@ -383,100 +321,35 @@ def prepare_geometry_fast(scene, cfg, mask_2ds, device="cuda", with_viewed=True,
     then the viewed frames) through pinned staging in one copy, poses inverted in one batched call, the cloud laid out
     on the device, and the viewed counts (bff_count_viewed) -- all enqueued on the current stream."""
     dev = torch.device(device)
-    if dev.type != "cuda":
-        return prepare_geometry(scene, cfg, mask_2ds, device=device, with_viewed=with_viewed)
-    staging = staging or Staging()
-    staging.wait()
-    h, w = int(cfg.height_2d), int(cfg.width_2d)
-    pts = np.asarray(scene.points)
-    if pts.dtype != np.float64 or pts.ndim != 2 or pts.shape[1] < 3 or not pts.flags.c_contiguous:
-        pts = np.ascontiguousarray(pts[:, :3], dtype=np.float64)
-    n, stride = pts.shape
-    n_pad = max(1024, ((n + 1023) // 1024) * 1024)
-    viewed = _viewed_ids_cached(scene, cfg.downsample_ratio) if with_viewed else []
-    ids = frame_union(mask_2ds, viewed)
-    inv = np.linalg.inv(np.stack([np.asarray(scene.poses[f], dtype=np.float64) for f in ids])).reshape(len(ids), 16) \
-        if ids else np.zeros((0, 16))
-    got = _depth_to_device(scene, ids, n, h, w, dev, staging, n_threads)
-    if got is None:
-        return prepare_geometry(scene, cfg, mask_2ds, device=device, with_viewed=with_viewed)
-    depth_dev, raw_keep, raw_size = got
-    xyz, unsort, perm, sort, bounds = _cloud_to_device(pts, n, stride, n_pad, dev, staging)
-    geom = SceneGeometry(scene_id=scene.scene_id, n_points=n, nw=(n + 63) // 64, height=h, width=w,
-                         cam_intr=np.asarray(scene.cam_intr, dtype=np.float64)[:3, :3].copy(), xyz=xyz, frame_ids=ids,
-                         inv_pose_host=inv, depth=depth_dev, depth_raw=raw_keep, depth_size=raw_size, tile_bounds=bounds,
-                         unsort=unsort[:n] if sort else None, perm=perm if sort else None, n_viewed=len(viewed),
-                         stage1=getattr(scene, "stage1", None))
-    if with_viewed:
-        count_geometry_viewed(geom, viewed)
-    staging.fence()
-    return geom
+    if dev.type == "cuda":
+        staging = staging or Staging()
+        staging.wait()
+        viewed = _viewed_ids_cached(scene, cfg.downsample_ratio) if with_viewed else []
+        geom = _geometry_to_device(scene, cfg, frame_union(mask_2ds, viewed), len(viewed), dev, staging, n_threads)
+        if geom is not None:
+            if with_viewed:
+                count_geometry_viewed(geom, viewed)
+            staging.fence()
+            return geom
+    return prepare_geometry(scene, cfg, mask_2ds, device=device, with_viewed=with_viewed)
 
 
 def prepare_class_fast(geom: SceneGeometry, mask_2d, cfg, staging: Staging = None, n_threads=4) -> DeviceScene:
     """scene.prepare_class with the run tables built natively into pinned staging and the small tables (frame table,
     label ids, inverse poses) uploaded as one block; only the class's own data crosses the bus."""
     dev = geom.xyz.device
-    if dev.type != "cuda":
-        return prepare_class(geom, mask_2d, cfg)
-    staging = staging or Staging()
-    staging.wait()
-    h, w = geom.height, geom.width
-    nb = lambda x: torch.as_tensor(x).to(dev, non_blocking=True)
-    word_bits = class_word_bits(mask_2d)
-    slots, f_mask, f_rowbase, f_nmask, vmo, all_rles, conf_list, labels, n_rows = \
-        class_frame_table(mask_2d, word_bits, geom.slot)
-    packed = pack_rles(all_rles, h * w, staging, "m2d", n_threads) if all_rles else None
-    if all_rles and packed is None:
-        return prepare_class(geom, mask_2d, cfg)                    # rare inputs: exact slow path
-    if packed is None:
-        z = torch.zeros(0, dtype=torch.int32)
-        packed = (z, z, torch.zeros(1, dtype=torch.int32))
-    run_start, run_end, run_offs = (nb(t) for t in packed)
-    conf_d = None
-    if conf_list:
-        dts = {c.dtype for c in conf_list}
-        if len(dts) != 1:
-            raise TypeError(f"mixed confidence dtypes {dts}")
-        if all(c.device.type == "cpu" and c.is_contiguous() for c in conf_list):
-            esz = conf_list[0].element_size()
-            meta = np.empty((2, len(conf_list)), dtype=np.int64)
-            meta[0] = [c.data_ptr() for c in conf_list]
-            meta[1] = [c.numel() * esz for c in conf_list]
-            total = int(meta[1].sum())
-            cstage = staging.get("conf", total)
-            if host_lib().bff_host_gather_bytes(meta[0].ctypes.data, meta[1].ctypes.data, len(conf_list), cstage.data_ptr()) != total:
-                raise ValueError("confidence tensors could not be gathered")
-            conf_d = cstage[:total].view(conf_list[0].dtype).to(dev, non_blocking=True)
-        else:
-            conf_d = torch.cat([c.reshape(-1) for c in conf_list]).to(dev)
-    else:
-        conf_d = torch.zeros(0, dtype=torch.float16, device=dev)
-    ids = {s: k for k, s in enumerate(dict.fromkeys(labels))}
-    label_id = np.zeros(len(labels), dtype=np.int32) if len(ids) <= 1 else \
-        np.fromiter(map(ids.__getitem__, labels), dtype=np.int32, count=len(labels))
-    nf = len(slots)
-    inv = geom.inv_pose_host[np.array(slots, dtype=np.int64)] if nf else np.zeros((0, 16))
-    tables = [np.asarray(a, dtype=np.int32) for a in (slots, f_mask, f_rowbase, f_nmask, np.zeros(nf, np.int32), vmo)] + [label_id]
-    sizes = [t.size for t in tables]
-    tstage = staging.get("tables", 4 * sum(sizes) + 8 * inv.size + 64).numpy()
-    np.concatenate(tables, out=tstage[:4 * sum(sizes)].view(np.int32))
-    at = (4 * sum(sizes) + 7) // 8 * 8
-    tstage[at:at + 8 * inv.size].view(np.float64)[:] = inv.reshape(-1)
-    tdev = staging.buf["tables"][:at + 8 * inv.size].to(dev, non_blocking=True)
-    tint = tdev[:4 * sum(sizes)].view(torch.int32)
-    cuts = np.cumsum([0] + sizes)
-    d_idx_d, f_mask_d, f_rowbase_d, f_nmask_d, f_flags_d, vmo_d, label_d = (tint[cuts[k]:cuts[k + 1]] for k in range(7))
-    inv_d = tdev[at:at + 8 * inv.size].view(torch.float64).view(nf, 16)
-    staging.fence()
-    return DeviceScene(
-        scene_id=geom.scene_id, n_points=geom.n_points, nw=geom.nw, height=h, width=w, cam_intr=geom.cam_intr, xyz=geom.xyz,
-        tile_bounds=geom.tile_bounds, depth=geom.depth, inv_pose=inv_d, depth_index=d_idx_d, frame_mask=f_mask_d,
-        frame_rowbase=f_rowbase_d, frame_nmask=f_nmask_d, frame_flags=f_flags_d, n_frames=nf, n_mask_frames=nf,
-        n_viewed=geom.n_viewed, word_bits=word_bits, n_rows=n_rows, run_start=run_start, run_end=run_end,
-        mask_run_offs=run_offs, view_mask_offs=vmo_d, conf=conf_d, labels=labels, label_id=label_d,
-        n_label_ids=max(1, len(ids)), stage1=geom.stage1, unsort=geom.unsort, perm=geom.perm, depth_raw=geom.depth_raw,
-        depth_size=geom.depth_size, viewed_in=geom.viewed, geometry=geom)
+    if dev.type == "cuda":
+        staging = staging or Staging()
+        staging.wait()
+        word_bits = class_word_bits(mask_2d)
+        ft = frame_table(mask_2d, word_bits, geom.slot.__getitem__)
+        runs = _run_tables(ft.rles, geom.height, geom.width, staging, dev, n_threads)
+        if runs is not None:
+            ds = _class_to_device(geom, ft, word_bits, runs, staging, True)
+            staging.fence()
+            return ds
+    return prepare_class(geom, mask_2d, cfg)                        # a CPU device, rare inputs: exact slow path
+
 
 def _viewed_ids_cached(scene, ratio):
     """scene.viewed_frame_ids (a sort of the ~3000 colour file names by their number) once per scene object."""
@@ -486,18 +359,6 @@ def _viewed_ids_cached(scene, ratio):
     if v is None:
         v = cache[key] = viewed_frame_ids(scene.color_files, ratio)
     return v
-
-
-_taps = {}
-
-
-def _taps_cache(hs, ws, h, w, dev):
-    key = (hs, ws, h, w, str(dev))
-    t = _taps.get(key)
-    if t is None:
-        from .io import bilinear_taps
-        t = _taps[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in bilinear_taps(hs, ws, h, w))
-    return t
 
 
 def prepare_stage1_fast(stage1: dict, device, staging: Staging, n_threads=2):
@@ -544,15 +405,22 @@ class Ingestor:
         host_lib()
         _lib.load()
 
-    def _work(self, scene):
+    def _loaded(self, item):
+        """This loader thread's (stream, staging buffers), made on first use, and `item` -- loaded here if it is a
+        loader (io.load_scene / io.load_scene_classes of one scene: the file reads run on this thread too; loaders that
+        take `staging` decode depth straight into pinned memory)."""
         tl = self.local
         if not hasattr(tl, "stream"):
             torch.cuda.set_device(self.device)
             tl.stream = torch.cuda.Stream(device=self.device)
             tl.staging = Staging()
-        if callable(scene):                           # a loader (e.g. io.load_scene of one scene): file reads run here too
-            # loaders that take `staging` decode depth straight into pinned memory
-            scene = scene(staging=tl.staging) if _takes_staging(scene) else scene()
+            tl.class_staging = Staging()              # the classes' small tables do not wait for the scene's depth copy
+        if callable(item):
+            item = item(staging=tl.staging) if _takes_staging(item) else item()
+        return tl, item
+
+    def _work(self, scene):
+        tl, scene = self._loaded(scene)
         with torch.cuda.stream(tl.stream):
             ds = prepare_scene_fast(scene, self.cfg, self.device, self.with_viewed, tl.staging, self.native_threads)
             st1 = None
@@ -568,16 +436,8 @@ class Ingestor:
 
     def _work_classes(self, item, classes):
         """One scene for several classes: (SceneGeometry, [DeviceScene per class], ready event)."""
-        tl = self.local
-        if not hasattr(tl, "stream"):
-            torch.cuda.set_device(self.device)
-            tl.stream = torch.cuda.Stream(device=self.device)
-            tl.staging = Staging()
-        if callable(item):                            # e.g. io.load_scene_classes of one scene
-            item = item(staging=tl.staging) if _takes_staging(item) else item()
+        tl, item = self._loaded(item)
         masks = [item.masks[c] for c in classes]
-        if not hasattr(tl, "class_staging"):
-            tl.class_staging = Staging()              # the classes' small tables do not wait for the scene's depth copy
         with torch.cuda.stream(tl.stream):
             geom = prepare_geometry_fast(item.scene, self.cfg, masks, self.device, self.with_viewed, tl.staging,
                                          self.native_threads)
@@ -611,9 +471,7 @@ def bench_host_inclusive(scenes, cfg, device, query, sim, steps=40, n_loaders=4,
                              for f, d in sc.depths.items()}
         # the decoded frames as a decoder with a page-locked output delivers them (io.decode_depth_pngs into pinned
         # memory): one pinned block in upload order, set up once -- the upload then reads it in place
-        with_viewed = (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
-        order = list(dict.fromkeys([fr["frame_id"][:-4] for fr in sc.mask_2d] +
-                                   (viewed_frame_ids(sc.color_files, cfg.downsample_ratio) if with_viewed else [])))
+        order = frame_union([sc.mask_2d], viewed_frame_ids(sc.color_files, cfg.downsample_ratio) if with_viewed_counts(cfg) else [])
         f0 = sc.depths_raw[order[0]]
         block = torch.empty((len(order),) + tuple(f0.shape), dtype=torch.int16).pin_memory()
         view = block.numpy().view(np.uint16)

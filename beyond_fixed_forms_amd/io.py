@@ -135,10 +135,10 @@ def load_scene(cfg, cls: str, scene_id: str, depth_on_device: bool = False, stag
     mask_2d = torch.load(os.path.join(cfg.mask_2d_dir, cls, f"{scene_id}.pth"), weights_only=False)
     color_dir = os.path.join(scene_dir, "color")
     color_files = [f for f in os.listdir(color_dir) if f.endswith(".jpg")] if os.path.isdir(color_dir) else []
-    from .scene import viewed_frame_ids
+    from .scene import viewed_frame_ids, with_viewed_counts
     # frames in upload order: mask frames in list order, then the frames only the detection-ratio sweep looks at
     need = list(dict.fromkeys(fr["frame_id"][:-4] for fr in mask_2d))
-    if (not cfg.if_occurance_threshold) and cfg.if_detected_ratio_threshold:
+    if with_viewed_counts(cfg):
         need = list(dict.fromkeys(need + viewed_frame_ids(color_files, cfg.downsample_ratio)))
     w, h = int(cfg.width_2d), int(cfg.height_2d)
     poses = {f: read_matrix_txt(os.path.join(scene_dir, "pose", f"{f}.txt")) for f in need}      # P:422
@@ -169,7 +169,7 @@ def load_scene_classes(cfg, classes, scene_id: str, depth_on_device: bool = Fals
     """load_scene for several query classes of one scene: the cloud, the poses and the depth frames are read ONCE --
     every frame any class's mask list names, then the detection-ratio sweep's frames -- plus each class's
     mask_2d/<cls>/<scene>.pth.  -> scene.SceneClasses (its `scene` holds an empty mask_2d)."""
-    from .scene import SceneClasses, frame_union, viewed_frame_ids
+    from .scene import SceneClasses, frame_union, viewed_frame_ids, with_viewed_counts
     scene_dir = os.path.join(cfg.scene_2d_dir, scene_id)
     cam_intr = read_matrix_txt(os.path.join(scene_dir, "intrinsic", "intrinsic_color.txt"))     # P:376
     points = np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"))                         # P:387
@@ -177,8 +177,7 @@ def load_scene_classes(cfg, classes, scene_id: str, depth_on_device: bool = Fals
              for cls in classes}
     color_dir = os.path.join(scene_dir, "color")
     color_files = [f for f in os.listdir(color_dir) if f.endswith(".jpg")] if os.path.isdir(color_dir) else []
-    viewed = viewed_frame_ids(color_files, cfg.downsample_ratio) \
-        if (not cfg.if_occurance_threshold) and cfg.if_detected_ratio_threshold else []
+    viewed = viewed_frame_ids(color_files, cfg.downsample_ratio) if with_viewed_counts(cfg) else []
     need = frame_union([masks[c] for c in classes], viewed)          # the geometry's slot order (upload order)
     w, h = int(cfg.width_2d), int(cfg.height_2d)
     poses = {f: read_matrix_txt(os.path.join(scene_dir, "pose", f"{f}.txt")) for f in need}      # P:422

@@ -164,8 +164,9 @@ def scene_struct(ds, stage1=None, n_frames=None):
 def params_struct(cfg, depth_thresh, filter_sort=False):
     _check_layout()
     p = ParamsStruct()
+    from .scene import with_viewed_counts
     p.filter_sort = 1 if filter_sort else 0
-    ratio = (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
+    ratio = with_viewed_counts(cfg)
     p.depth_thresh = float(depth_thresh)
     p.filter_mode = 1 if cfg.if_occurance_threshold else (2 if ratio else 0)
     p.filter_fraction = float(cfg.detected_ratio_threshold if ratio else cfg.occurance_threshold)
@@ -407,12 +408,13 @@ def project_stream(scenes, cfg, device, consume, n_loaders=2, with_stage1=True, 
     surfaces at that scene's turn."""
     from .ingest import Ingestor
     from .projection import projection_back, projection_front
+    from .scene import with_viewed_counts
     dev = torch.device(device)
     depth = PIPELINE_DEPTH if depth is None else depth
     n = len(scenes)
     if n == 0:
         return
-    with_viewed = (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
+    with_viewed = with_viewed_counts(cfg)
     if dev.type != "cuda":                      # host tensors: no streams, no loaders (the kernels themselves need the GPU)
         from .refinement import prepare_stage1
         from .scene import prepare_scene

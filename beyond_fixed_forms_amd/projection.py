@@ -17,7 +17,8 @@ import torch
 import os
 
 from . import _lib, pipeline
-from .scene import DEPTH_THRESH, DeviceScene, prepare_scene
+from .scene import (DEPTH_THRESH, DeviceScene, prepare_class, prepare_geometry, prepare_scene,
+                    with_viewed_counts)
 from .timing import merge_span, span, sweep_span
 
 
@@ -199,7 +200,7 @@ def projection_front(ds: DeviceScene, cfg, debug_out: bool = False, timers=None,
     and components are issued one by one and `projection_back` continues on the host."""
     if fast is None:
         fast = not debug_out
-    do_ratio = (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
+    do_ratio = with_viewed_counts(cfg)
     # one class of a multi-class run (scene.prepare_class): the viewed counts were computed once for the scene
     viewed_in = ds.viewed_in if do_ratio else None
     if do_ratio and ds.geometry is not None and viewed_in is None:
@@ -223,7 +224,7 @@ def _projection_front(ds, cfg, debug_out, timers, viewed_in=None) -> _Front:
     dev = ds.xyz.device
     fr = _Front(ds, cfg, {}, debug_out)
     n, nw = ds.n_points, ds.nw
-    do_ratio = fr.do_ratio = (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
+    do_ratio = fr.do_ratio = with_viewed_counts(cfg)
 
     # a1: RLE -> per-pixel mask words (never the dense (M,1,H,W) tensors of P:400)
     n_mviews = ds.view_mask_offs.shape[0] - 1
@@ -533,7 +534,7 @@ def _projection_back(fr: _Front, timers, phases, stage1=None) -> Stage2Result:
 def project_scene(scene, cfg, device="cuda", return_result: bool = False, debug_out: bool = False):
     """Reference-shaped entry point: in-memory scene inputs -> the dict saved at P:630-634."""
     _lib.load()                                     # fail loudly before any work if the library is missing
-    with_viewed = (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
+    with_viewed = with_viewed_counts(cfg)
     if torch.device(device).type == "cuda" and not debug_out:
         from .ingest import prepare_scene_fast      # native run tables, packed pinned uploads, cloud laid out on the device
         ds = prepare_scene_fast(scene, cfg, device=device, with_viewed=with_viewed)
@@ -551,7 +552,6 @@ def project_scene_classes(scene, masks: dict, cfg, device="cuda", return_result:
     Every class's result is bit-identical to project_scene on a scene whose mask_2d is that class's list.
     raw_depth_resident (plain preparation only, i.e. debug_out or a CPU device): as scene.prepare_scene."""
     _lib.load()
-    from .scene import prepare_class, prepare_geometry, with_viewed_counts
     classes = list(masks)
     lists = [masks[c] for c in classes]
     with_viewed = with_viewed_counts(cfg)

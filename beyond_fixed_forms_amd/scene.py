@@ -5,6 +5,12 @@ Mirrors the loading part of the reference scene loop (tools/projection_2d_to_3d.
 `np.linalg.inv(pose)` (kept on the host in float64, exactly as the reference computes it), depth
 images, and the RLE `mask_2d` list -- which is turned into flat run tables instead of being decoded
 to dense (M,1,H,W) tensors.
+
+prepare_scene (one mask list) and prepare_geometry + prepare_class (several lists against one resident
+scene) are put together from the same pieces: cloud_host_layout, host_depth_to_device /
+raw_depth_on_device, frame_table, concat_confidences, label_ids, and device_scene, the one place a
+DeviceScene is assembled from a SceneGeometry and one list's tables.  ingest.py builds the same
+records from the same frame table through pinned staging and native code.
 """
 from __future__ import annotations
 
@@ -165,159 +171,204 @@ def viewed_frame_ids(color_files, downsample_ratio):
     return [f[:-4] for f in files[::downsample_ratio]]
 
 
-def prepare_scene(scene, cfg, device="cuda", with_viewed=True, sort_points=True, raw_depth_resident=None) -> DeviceScene:
-    """Upload one scene.  `scene` is duck-typed like beyond_fixed_forms_amd.synthetic.SceneInputs
-    (the reference's on-disk objects held in memory)."""
-    dev = torch.device(device)
-    h, w = int(cfg.height_2d), int(cfg.width_2d)
-    pts = np.asarray(scene.points)[:, :3].astype(np.float64, copy=False)          # :387
+def with_viewed_counts(cfg) -> bool:
+    """The detection-ratio filter (P:524-578) is the one that needs viewed counts."""
+    return (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The pieces every preparation function is made of.  The cloud, the poses, the depth frames and the detection ratio's
+# viewed counts depend on the scene alone (P:538-567 never looks at a mask): they make a SceneGeometry.  A mask_2d list
+# adds a frame table, run tables, confidences and labels: together a DeviceScene.  prepare_scene builds both for one
+# list; prepare_geometry + prepare_class share one geometry among several lists (pipeline.project_classes_stream,
+# projection.project_scene_classes), each class bit-identical to prepare_scene on that class's own scene.  ingest.py
+# builds the same records through pinned staging and native code.
+
+def padded_points(n):
+    return max(1024, ((n + 1023) // 1024) * 1024)
+
+
+def cloud_host_layout(points, sort_points=True):
+    """(N, >= 3) cloud -> (f64 [3][n_pad] SoA in Morton order, perm, unsort, n, n_pad); perm / unsort are None when the
+    cloud is left as it is.  Sorted position s holds original point perm[s]; unsort is the inverse."""
+    pts = np.asarray(points)[:, :3].astype(np.float64, copy=False)                  # :387
     n = pts.shape[0]
-    nw = (n + 63) // 64
-    n_pad = max(1024, ((n + 1023) // 1024) * 1024)
+    n_pad = padded_points(n)
     soa = np.zeros((3, n_pad), dtype=np.float64)
     unsort = perm = None
     if sort_points and n > 1:
-        perm = morton_order(pts)                    # sorted position s holds original point perm[s]
+        perm = morton_order(pts)
         soa[:, :n] = pts[perm].T
         unsort = np.empty(n, dtype=np.int32)
         unsort[perm] = np.arange(n, dtype=np.int32)
     else:
         soa[:, :n] = pts.T
-    cam_intr = np.asarray(scene.cam_intr, dtype=np.float64)[:3, :3].copy()          # :376
+    return soa, perm, unsort, n, n_pad
 
-    # ---- frame table: every 2-D mask frame in list order (chunks of <= word_bits masks), then the
-    # frames of the detection-ratio sweep that carry no masks
-    max_m = max((len(fr["segmented_frame_masks"]) for fr in scene.mask_2d), default=0)
-    word_bits = 32 if max_m <= 32 else 64
-    viewed = viewed_frame_ids(scene.color_files, cfg.downsample_ratio) if with_viewed else []
-    viewed_left = dict.fromkeys(viewed)              # ordered set of frames still to be counted
-    depth_slot, depth_list = {}, []
-    raw_depth = getattr(scene, "depths_raw", None)
+
+def class_word_bits(mask_2d):
+    """32-bit mask words unless some frame of the list holds more than 32 masks (chosen per scene / per class)."""
+    max_m = max((len(fr["segmented_frame_masks"]) for fr in mask_2d), default=0)
+    return 32 if max_m <= 32 else 64
+
+
+def slots_on_first_use():
+    """Depth slots of a single-class scene: `slot(fid)` gives a frame the next free slot when it is first asked for
+    (mask frames that hold at least one mask in list order, then the viewed frames not yet seen).
+    -> (slot, the frame ids in slot order, filled as slot is called)."""
+    slot_of, ids = {}, []
 
     def slot(fid):
-        if fid not in depth_slot:
-            if raw_depth is not None:                 # uploaded as uint16, scaled + resized on the device
-                d = np.asarray(raw_depth[fid])
-                if d.dtype != np.uint16 or d.ndim != 2:
-                    raise ValueError(f"raw depth {fid}: expected a 2-D uint16 array")
-                depth_list.append(d)
-            else:
-                d = np.asarray(scene.depths[fid], dtype=np.float32)
-                if d.shape != (h, w):
-                    raise ValueError(f"depth {fid}: shape {d.shape} != ({h},{w})")
-                depth_list.append(d.reshape(-1))
-            depth_slot[fid] = len(depth_list) - 1
-        return depth_slot[fid]
+        s = slot_of.get(fid)
+        if s is None:
+            s = slot_of[fid] = len(ids)
+            ids.append(fid)
+        return s
+    return slot, ids
 
-    inv, d_idx, f_mask, f_rowbase, f_nmask, f_flags = [], [], [], [], [], []
+
+@dataclasses.dataclass
+class FrameTable:
+    """The kernel frames of one mask_2d list (frame_table) and the per-mask rows that go with them."""
+    frame_ids: List[str]                 # per kernel frame: whose pose it takes
+    depth_index: List[int]               # the tables of DeviceScene, as lists
+    frame_mask: List[int]
+    frame_rowbase: List[int]
+    frame_nmask: List[int]
+    frame_flags: List[int]
+    view_mask_offs: List[int]
+    rles: list                           # every 2-D mask, in row order
+    conf_list: list                      # one confidence tensor per mask_2d entry
+    labels: List[str]
+    n_rows: int
+    n_mask_frames: int
+
+    def int_tables(self):
+        return [np.asarray(a, dtype=np.int32) for a in (self.depth_index, self.frame_mask, self.frame_rowbase,
+                                                        self.frame_nmask, self.frame_flags, self.view_mask_offs)]
+
+
+def frame_table(mask_2d, word_bits, slot, viewed=None) -> FrameTable:
+    """Every 2-D mask frame in list order, in chunks of <= word_bits masks (P:413-421; an entry without masks makes no
+    kernel frame), `slot(fid)` naming the depth slot of each.  With `viewed` (the ordered frame ids of the
+    detection-ratio sweep, P:538-567) the first chunk of a mask frame that is viewed carries flag bit 0 and the viewed
+    frames left over follow as frames without masks; without, all flags are 0 and the viewed counts come from elsewhere
+    (SceneGeometry.viewed)."""
+    viewed_left = dict.fromkeys(viewed or ())        # ordered set of frames still to be counted
+    frame_ids, d_idx, f_mask, f_rowbase, f_nmask, f_flags = [], [], [], [], [], []
     all_rles, view_mask_offs, conf_list, labels = [], [0], [], []
     row = 0
-    for fr in scene.mask_2d:                                                        # :413-421
+    for fr in mask_2d:
         fid = fr["frame_id"][:-4]
         rles = fr["segmented_frame_masks"]
         m = len(rles)
         if not (len(fr["confidences"]) == m and len(fr["labels"]) == m):
             raise ValueError(f"frame {fid}: masks / confidences / labels differ in length")
-        ipose = np.linalg.inv(np.asarray(scene.poses[fid], dtype=np.float64))       # :425
-        first = True
         for c0 in range(0, m, word_bits):
             mc = min(word_bits, m - c0)
-            inv.append(ipose); d_idx.append(slot(fid))
+            frame_ids.append(fid); d_idx.append(slot(fid))
             f_mask.append(len(view_mask_offs) - 1); f_rowbase.append(row); f_nmask.append(mc)
-            counted = first and fid in viewed_left
+            counted = c0 == 0 and fid in viewed_left
             if counted:
                 del viewed_left[fid]
             f_flags.append(1 if counted else 0)
-            first = False
-            all_rles += list(rles[c0:c0 + mc])
             view_mask_offs.append(view_mask_offs[-1] + mc)
             row += mc
+        all_rles += rles
         conf_list.append(fr["confidences"])
-        labels += list(fr["labels"])
-    n_mask_frames = len(inv)
-    for fid in viewed_left:                                                         # :538-567
-        inv.append(np.linalg.inv(np.asarray(scene.poses[fid], dtype=np.float64)))
-        d_idx.append(slot(fid)); f_mask.append(-1); f_rowbase.append(0); f_nmask.append(0); f_flags.append(1)
+        labels += fr["labels"]
+    n_mask_frames = len(frame_ids)
+    for fid in viewed_left:
+        frame_ids.append(fid); d_idx.append(slot(fid))
+        f_mask.append(-1); f_rowbase.append(0); f_nmask.append(0); f_flags.append(1)
+    return FrameTable(frame_ids, d_idx, f_mask, f_rowbase, f_nmask, f_flags, view_mask_offs, all_rles, conf_list, labels,
+                      row, n_mask_frames)
 
-    for r in all_rles:
-        if int(r["length"]) != h * w:
-            raise ValueError(f"mask RLE length {r['length']} != H*W = {h * w}")
-    rs, re, roffs = runs_from_rles(all_rles, "2-D mask")
-    if conf_list:
-        dts = {c.dtype for c in conf_list}
-        if len(dts) != 1:
-            raise TypeError(f"mixed confidence dtypes {dts}")
-        conf = torch.cat([c.reshape(-1).cpu() for c in conf_list])
-    else:
-        conf = torch.zeros(0, dtype=torch.float16)
-    ids = {}
-    label_id = np.array([ids.setdefault(s, len(ids)) for s in labels], dtype=np.int32)
 
-    def t(a, dtype):
-        return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(dev)
+def confidence_dtype(conf_list):
+    dts = {c.dtype for c in conf_list}
+    if len(dts) != 1:
+        raise TypeError(f"mixed confidence dtypes {dts}")
+    return dts.pop()
 
-    nf = len(inv)
-    raw_keep = raw_size = None
 
-    def frames_to_device(frames, np_dtype, torch_dtype):
-        """list of equally shaped host arrays -> one device tensor [F][...], frame by frame (no 1.5 GB np.stack:
-        the copies go straight from the callers' arrays)."""
-        out = torch.empty((len(frames),) + tuple(frames[0].shape), dtype=torch_dtype, device=dev)
-        for i, f in enumerate(frames):
-            out[i].copy_(torch.from_numpy(np.ascontiguousarray(f, dtype=np_dtype)))
-        return out
+def concat_confidences(conf_list, on_host=True):
+    """One (Ins,) tensor of the frames' confidences, on the host or (on_host=False) wherever they are."""
+    if not conf_list:
+        return torch.zeros(0, dtype=torch.float16)
+    confidence_dtype(conf_list)
+    return torch.cat([c.reshape(-1).cpu() if on_host else c.reshape(-1) for c in conf_list])
 
-    if raw_depth is not None and depth_list:
-        from . import _lib
+
+def label_ids(labels):
+    """-> (int32 id per label, number of distinct strings): ids in order of first appearance."""
+    ids = {s: k for k, s in enumerate(dict.fromkeys(labels))}
+    if len(ids) <= 1:
+        return np.zeros(len(labels), dtype=np.int32), len(ids)
+    return np.fromiter(map(ids.__getitem__, labels), dtype=np.int32, count=len(labels)), len(ids)
+
+
+_taps = {}
+
+
+def resize_taps(hs, ws, h, w, dev):
+    """io.bilinear_taps of (hs, ws) -> (h, w) as device tensors, built once per size combination and device."""
+    key = (hs, ws, h, w, str(dev))
+    t = _taps.get(key)
+    if t is None:
         from .io import bilinear_taps
-        hs, ws = depth_list[0].shape
-        if any(d.shape != (hs, ws) for d in depth_list):
-            raise ValueError("raw depth frames of different sizes")
-        taps = None
-        if (hs, ws) != (h, w):
-            taps = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in bilinear_taps(hs, ws, h, w))
-        raw_dev = frames_to_device([d.view(np.int16) for d in depth_list], np.int16, torch.int16)
-        if keep_raw_depth(n, h, w) if raw_depth_resident is None else raw_depth_resident:
-            depth_dev, raw_keep = None, raw_dev
-            if tile_raw_depth():
-                raw_keep, raw_size = _lib.tile_depth(raw_dev, metres=tile_raw_depth() == "f32"), (hs, ws)
+        t = _taps[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in bilinear_taps(hs, ws, h, w))
+    return t
+
+
+def raw_depth_on_device(raw_dev, n_points, h, w, raw_depth_resident=None):
+    """int16 [F][hs][ws] on the device (the PNGs' uint16 millimetres) -> (depth, depth_raw, depth_size) as DeviceScene
+    holds them: resident at the sensor's resolution (keep_raw_depth, or as raw_depth_resident says), tiled unless
+    BFF_DEPTH_TILES=0, or scaled + resized to float32 (H, W) images here (P:432-436)."""
+    from . import _lib
+    hs, ws = int(raw_dev.shape[1]), int(raw_dev.shape[2])
+    if keep_raw_depth(n_points, h, w) if raw_depth_resident is None else raw_depth_resident:
+        tiles = tile_raw_depth()
+        if tiles:
+            return None, _lib.tile_depth(raw_dev, metres=tiles == "f32"), (hs, ws)
+        return None, raw_dev, None
+    taps = resize_taps(hs, ws, h, w, raw_dev.device) if (hs, ws) != (h, w) else None
+    return _lib.depth_from_u16(raw_dev, h, w, taps), None, None
+
+
+def host_depth_to_device(scene, ids, n_points, h, w, dev, raw_depth_resident=None):
+    """The depth frames `ids` of a scene, one slot each in that order -> (depth, depth_raw, depth_size): raw uint16
+    frames (scene.depths_raw) uploaded as they are and handed to raw_depth_on_device, else float32 (H, W) metres."""
+    raw = getattr(scene, "depths_raw", None)
+    if not ids:
+        return torch.zeros((0, h * w), dtype=torch.float32, device=dev), None, None
+    frames = []
+    for f in ids:
+        if raw is not None:
+            d = np.asarray(raw[f])
+            if d.dtype != np.uint16 or d.ndim != 2:
+                raise ValueError(f"raw depth {f}: expected a 2-D uint16 array")
+            frames.append(d.view(np.int16))
         else:
-            depth_dev = _lib.depth_from_u16(raw_dev, h, w, taps)
-    elif depth_list:
-        depth_dev = frames_to_device(depth_list, np.float32, torch.float32)
-    else:
-        depth_dev = torch.zeros((0, h * w), dtype=torch.float32, device=dev)
-    xyz_dev = t(soa, torch.float64)
-    bounds = None
-    if dev.type == "cuda" and n:
-        from . import _lib
-        bounds = _lib.point_tile_bounds(xyz_dev, n)      # built once per scene, next to the spatial sort it relies on
-    return DeviceScene(
-        scene_id=scene.scene_id, n_points=n, nw=nw, height=h, width=w, cam_intr=cam_intr,
-        xyz=xyz_dev, tile_bounds=bounds,
-        depth=depth_dev,
-        inv_pose=t(np.stack(inv).reshape(nf, 16) if nf else np.zeros((0, 16)), torch.float64),
-        depth_index=t(np.array(d_idx, np.int32), torch.int32), frame_mask=t(np.array(f_mask, np.int32), torch.int32),
-        frame_rowbase=t(np.array(f_rowbase, np.int32), torch.int32),
-        frame_nmask=t(np.array(f_nmask, np.int32), torch.int32), frame_flags=t(np.array(f_flags, np.int32), torch.int32),
-        n_frames=nf, n_mask_frames=n_mask_frames, n_viewed=len(viewed), word_bits=word_bits, n_rows=row,
-        run_start=t(rs, torch.int32), run_end=t(re, torch.int32), mask_run_offs=t(roffs, torch.int32),
-        view_mask_offs=t(np.array(view_mask_offs, np.int32), torch.int32),
-        conf=conf.to(dev), labels=labels, label_id=t(label_id, torch.int32), n_label_ids=max(1, len(ids)),
-        stage1=getattr(scene, "stage1", None), unsort=None if unsort is None else t(unsort, torch.int32),
-        perm=None if perm is None else t(perm.astype(np.int32), torch.int32), depth_raw=raw_keep, depth_size=raw_size)
+            d = np.asarray(scene.depths[f], dtype=np.float32)
+            if d.shape != (h, w):
+                raise ValueError(f"depth {f}: shape {d.shape} != ({h},{w})")
+            frames.append(d.reshape(-1))
+    if any(d.shape != frames[0].shape for d in frames):
+        raise ValueError("raw depth frames of different sizes")
+    # frame by frame (no 1.5 GB np.stack: the copies go straight from the caller's arrays)
+    out = torch.empty((len(frames),) + frames[0].shape, dtype=torch.float32 if raw is None else torch.int16, device=dev)
+    for i, d in enumerate(frames):
+        out[i].copy_(torch.from_numpy(np.ascontiguousarray(d)))
+    return (out, None, None) if raw is None else raw_depth_on_device(out, n_points, h, w, raw_depth_resident)
 
-
-# ---------------------------------------------------------------------------------------------------------------------
-# Several query classes of one scene (pipeline.project_classes_stream, projection.project_scene_classes): the cloud, the
-# poses, the depth frames and the detection ratio's viewed counts depend on the scene alone (P:538-567 never looks at a
-# mask), so they are prepared once (SceneGeometry) and every class adds only its run tables, confidences and labels
-# (prepare_class).  Each class's result is bit-identical to prepare_scene + the single-class path on that class's scene.
 
 @dataclasses.dataclass
 class SceneGeometry:
-    """One scene resident for many classes: sorted cloud, one inverse pose and one depth slot per frame id (the union of
-    the classes' mask frames, in class then list order, then the viewed frames), and the viewed counts."""
+    """The part of a resident scene that no mask touches: sorted cloud, one inverse pose and one depth slot per frame
+    id, and -- shared by the classes of a multi-class run -- the viewed counts.  Slot order: prepare_geometry takes
+    frame_union (the classes' mask frames, in class then list order, then the viewed frames); prepare_scene the order
+    its one frame table first asks for them (slots_on_first_use)."""
     scene_id: str
     n_points: int
     nw: int
@@ -345,6 +396,75 @@ class SceneGeometry:
         return self.depth_raw if self.depth_raw is not None else self.depth
 
 
+def new_geometry(scene, h, w, n, ids, inv, n_viewed, xyz, depth3, bounds, unsort, perm) -> SceneGeometry:
+    """depth3: (depth, depth_raw, depth_size); the scene gives its id, its intrinsics `[:3,:3]` (:376) and stage 1."""
+    return SceneGeometry(scene_id=scene.scene_id, n_points=n, nw=(n + 63) // 64, height=h, width=w,
+                         cam_intr=np.asarray(scene.cam_intr, dtype=np.float64)[:3, :3].copy(), xyz=xyz, frame_ids=ids,
+                         inv_pose_host=inv, depth=depth3[0], depth_raw=depth3[1], depth_size=depth3[2], tile_bounds=bounds,
+                         unsort=unsort, perm=perm, n_viewed=n_viewed, stage1=getattr(scene, "stage1", None))
+
+
+def device_scene(geom: SceneGeometry, ft: FrameTable, word_bits, tables, inv_pose, runs, conf, n_label_ids,
+                 shared) -> DeviceScene:
+    """A geometry + one list's tables on the device: `tables` = FrameTable.int_tables() and the label ids, `runs` =
+    (run_start, run_end, mask_run_offs).  shared: one class of a multi-class run, which keeps the geometry and takes
+    its viewed counts; a single-class scene keeps neither and counts `viewed` inside its own sweep."""
+    depth_index, frame_mask, frame_rowbase, frame_nmask, frame_flags, view_mask_offs, label_id = tables
+    return DeviceScene(
+        scene_id=geom.scene_id, n_points=geom.n_points, nw=geom.nw, height=geom.height, width=geom.width,
+        cam_intr=geom.cam_intr, xyz=geom.xyz, tile_bounds=geom.tile_bounds, depth=geom.depth, inv_pose=inv_pose,
+        depth_index=depth_index, frame_mask=frame_mask, frame_rowbase=frame_rowbase, frame_nmask=frame_nmask,
+        frame_flags=frame_flags, n_frames=len(ft.frame_ids), n_mask_frames=ft.n_mask_frames, n_viewed=geom.n_viewed,
+        word_bits=word_bits, n_rows=ft.n_rows, run_start=runs[0], run_end=runs[1], mask_run_offs=runs[2],
+        view_mask_offs=view_mask_offs, conf=conf, labels=ft.labels, label_id=label_id, n_label_ids=max(1, n_label_ids),
+        stage1=geom.stage1, unsort=geom.unsort, perm=geom.perm, depth_raw=geom.depth_raw, depth_size=geom.depth_size,
+        viewed_in=geom.viewed if shared else None, geometry=geom if shared else None)
+
+
+def class_inv_poses(geom, ft):
+    """f64 [F][16]: the inverse pose of each kernel frame, out of its depth slot's."""
+    return geom.inv_pose_host[np.asarray(ft.depth_index, dtype=np.int64)].reshape(len(ft.frame_ids), 16)
+
+
+def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -> SceneGeometry:
+    h, w = int(cfg.height_2d), int(cfg.width_2d)
+    soa, perm, unsort, n, _ = cloud_host_layout(scene.points, sort_points)
+    inv = np.stack([np.linalg.inv(np.asarray(scene.poses[f], dtype=np.float64)).reshape(16) for f in ids]) if ids \
+        else np.zeros((0, 16))                                                      # :425
+    depth3 = host_depth_to_device(scene, ids, n, h, w, dev, raw_depth_resident)
+    xyz = torch.as_tensor(soa).to(dev)
+    bounds = None
+    if dev.type == "cuda" and n:
+        from . import _lib
+        bounds = _lib.point_tile_bounds(xyz, n)          # built once per scene, next to the spatial sort it relies on
+    t32 = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+    return new_geometry(scene, h, w, n, ids, inv, n_viewed, xyz, depth3, bounds, t32(unsort), t32(perm))
+
+
+def _class_tables(geom, ft, word_bits, dev, shared) -> DeviceScene:
+    for r in ft.rles:
+        if int(r["length"]) != geom.height * geom.width:
+            raise ValueError(f"mask RLE length {r['length']} != H*W = {geom.height * geom.width}")
+    runs = runs_from_rles(ft.rles, "2-D mask")
+    conf = concat_confidences(ft.conf_list)
+    label_id, n_ids = label_ids(ft.labels)
+    t = lambda a, dtype=torch.int32: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(dev)
+    return device_scene(geom, ft, word_bits, [t(a) for a in ft.int_tables() + [label_id]],
+                        t(class_inv_poses(geom, ft), torch.float64), [t(a) for a in runs], conf.to(dev), n_ids, shared)
+
+
+def prepare_scene(scene, cfg, device="cuda", with_viewed=True, sort_points=True, raw_depth_resident=None) -> DeviceScene:
+    """Upload one scene.  `scene` is duck-typed like beyond_fixed_forms_amd.synthetic.SceneInputs
+    (the reference's on-disk objects held in memory)."""
+    dev = torch.device(device)
+    viewed = viewed_frame_ids(scene.color_files, cfg.downsample_ratio) if with_viewed else []
+    word_bits = class_word_bits(scene.mask_2d)
+    slot, ids = slots_on_first_use()
+    ft = frame_table(scene.mask_2d, word_bits, slot, viewed)
+    geom = _geometry(scene, cfg, ids, len(viewed), dev, sort_points, raw_depth_resident)
+    return _class_tables(geom, ft, word_bits, dev, shared=False)
+
+
 @dataclasses.dataclass
 class SceneClasses:
     """One scene's inputs for several query classes: `scene` is SceneInputs-like (its own mask_2d is not used), `masks`
@@ -357,42 +477,6 @@ def frame_union(mask_2ds, viewed_ids=()):
     """Frame ids of several mask_2d lists (in list order, list after list), then the viewed frames: each id once."""
     ids = [fr["frame_id"][:-4] for m in mask_2ds for fr in m]
     return list(dict.fromkeys(ids + list(viewed_ids)))
-
-
-def class_word_bits(mask_2d):
-    """32-bit mask words unless some frame of the class holds more than 32 masks (chosen per class, as prepare_scene)."""
-    max_m = max((len(fr["segmented_frame_masks"]) for fr in mask_2d), default=0)
-    return 32 if max_m <= 32 else 64
-
-
-def class_frame_table(mask_2d, word_bits, slot_of):
-    """prepare_scene's frame table of the mask frames alone (frame_flags all 0: the viewed counts come from the
-    geometry): (slots, f_mask, f_rowbase, f_nmask, view_mask_offs, rles, conf_list, labels, n_rows)."""
-    slots, f_mask, f_rowbase, f_nmask = [], [], [], []
-    all_rles, view_mask_offs, conf_list, labels = [], [0], [], []
-    row = 0
-    for fr in mask_2d:
-        fid = fr["frame_id"][:-4]
-        rles = fr["segmented_frame_masks"]
-        m = len(rles)
-        if not (len(fr["confidences"]) == m and len(fr["labels"]) == m):
-            raise ValueError(f"frame {fid}: masks / confidences / labels differ in length")
-        s = slot_of[fid]
-        for c0 in range(0, m, word_bits):
-            mc = min(word_bits, m - c0)
-            slots.append(s)
-            f_mask.append(len(view_mask_offs) - 1); f_rowbase.append(row); f_nmask.append(mc)
-            view_mask_offs.append(view_mask_offs[-1] + mc)
-            row += mc
-        all_rles += list(rles)
-        conf_list.append(fr["confidences"])
-        labels += list(fr["labels"])
-    return slots, f_mask, f_rowbase, f_nmask, view_mask_offs, all_rles, conf_list, labels, row
-
-
-def with_viewed_counts(cfg) -> bool:
-    """The detection-ratio filter (P:524-578) is the one that needs viewed counts."""
-    return (not cfg.if_occurance_threshold) and bool(cfg.if_detected_ratio_threshold)
 
 
 def count_geometry_viewed(geom: SceneGeometry, viewed_ids, depth_thresh=DEPTH_THRESH):
@@ -414,70 +498,10 @@ def prepare_geometry(scene, cfg, mask_2ds, device="cuda", with_viewed=True, sort
                      raw_depth_resident=None) -> SceneGeometry:
     """The class-independent part of prepare_scene for the classes whose mask lists are `mask_2ds`: cloud (sorted),
     inverse poses and depth of every frame any of them or the detection-ratio sweep looks at, and -- with_viewed, on a
-    GPU -- the viewed counts (bff_count_viewed).  Same conversions and layout rules as prepare_scene."""
+    GPU -- the viewed counts (bff_count_viewed)."""
     dev = torch.device(device)
-    h, w = int(cfg.height_2d), int(cfg.width_2d)
-    pts = np.asarray(scene.points)[:, :3].astype(np.float64, copy=False)
-    n = pts.shape[0]
-    n_pad = max(1024, ((n + 1023) // 1024) * 1024)
-    soa = np.zeros((3, n_pad), dtype=np.float64)
-    unsort = perm = None
-    if sort_points and n > 1:
-        perm = morton_order(pts)
-        soa[:, :n] = pts[perm].T
-        unsort = np.empty(n, dtype=np.int32)
-        unsort[perm] = np.arange(n, dtype=np.int32)
-    else:
-        soa[:, :n] = pts.T
     viewed = viewed_frame_ids(scene.color_files, cfg.downsample_ratio) if with_viewed else []
-    ids = frame_union(mask_2ds, viewed)
-    inv = np.stack([np.linalg.inv(np.asarray(scene.poses[f], dtype=np.float64)).reshape(16) for f in ids]) if ids \
-        else np.zeros((0, 16))
-    raw_depth = getattr(scene, "depths_raw", None)
-    raw_keep = raw_size = None
-    if raw_depth is not None and ids:
-        from . import _lib
-        from .io import bilinear_taps
-        frames = []
-        for f in ids:
-            d = np.asarray(raw_depth[f])
-            if d.dtype != np.uint16 or d.ndim != 2:
-                raise ValueError(f"raw depth {f}: expected a 2-D uint16 array")
-            frames.append(d)
-        hs, ws = frames[0].shape
-        if any(d.shape != (hs, ws) for d in frames):
-            raise ValueError("raw depth frames of different sizes")
-        raw_dev = torch.empty((len(frames), hs, ws), dtype=torch.int16, device=dev)
-        for i, d in enumerate(frames):
-            raw_dev[i].copy_(torch.from_numpy(np.ascontiguousarray(d).view(np.int16)))
-        if keep_raw_depth(n, h, w) if raw_depth_resident is None else raw_depth_resident:
-            depth_dev, raw_keep = None, raw_dev
-            if tile_raw_depth():
-                raw_keep, raw_size = _lib.tile_depth(raw_dev, metres=tile_raw_depth() == "f32"), (hs, ws)
-        else:
-            taps = None
-            if (hs, ws) != (h, w):
-                taps = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in bilinear_taps(hs, ws, h, w))
-            depth_dev = _lib.depth_from_u16(raw_dev, h, w, taps)
-    elif ids:
-        depth_dev = torch.empty((len(ids), h * w), dtype=torch.float32, device=dev)
-        for i, f in enumerate(ids):
-            d = np.asarray(scene.depths[f], dtype=np.float32)
-            if d.shape != (h, w):
-                raise ValueError(f"depth {f}: shape {d.shape} != ({h},{w})")
-            depth_dev[i].copy_(torch.from_numpy(np.ascontiguousarray(d).reshape(-1)))
-    else:
-        depth_dev = torch.zeros((0, h * w), dtype=torch.float32, device=dev)
-    xyz_dev = torch.as_tensor(soa).to(dev)
-    bounds = None
-    if dev.type == "cuda" and n:
-        from . import _lib
-        bounds = _lib.point_tile_bounds(xyz_dev, n)
-    t32 = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-    geom = SceneGeometry(scene_id=scene.scene_id, n_points=n, nw=(n + 63) // 64, height=h, width=w,
-                         cam_intr=np.asarray(scene.cam_intr, dtype=np.float64)[:3, :3].copy(), xyz=xyz_dev, frame_ids=ids,
-                         inv_pose_host=inv, depth=depth_dev, depth_raw=raw_keep, depth_size=raw_size, tile_bounds=bounds,
-                         unsort=t32(unsort), perm=t32(perm), n_viewed=len(viewed), stage1=getattr(scene, "stage1", None))
+    geom = _geometry(scene, cfg, frame_union(mask_2ds, viewed), len(viewed), dev, sort_points, raw_depth_resident)
     if with_viewed and dev.type == "cuda":
         count_geometry_viewed(geom, viewed)
     return geom
@@ -488,34 +512,5 @@ def prepare_class(geom: SceneGeometry, mask_2d, cfg, device=None) -> DeviceScene
     frame table of its mask frames in list order whose depth_index points into the geometry's depth slots.  Frame,
     mask, label and confidence tables equal prepare_scene's for the class's own scene (with_viewed=False)."""
     dev = geom.xyz.device if device is None else torch.device(device)
-    h, w = geom.height, geom.width
     word_bits = class_word_bits(mask_2d)
-    slots, f_mask, f_rowbase, f_nmask, vmo, all_rles, conf_list, labels, n_rows = \
-        class_frame_table(mask_2d, word_bits, geom.slot)
-    for r in all_rles:
-        if int(r["length"]) != h * w:
-            raise ValueError(f"mask RLE length {r['length']} != H*W = {h * w}")
-    rs, re, roffs = runs_from_rles(all_rles, "2-D mask")
-    if conf_list:
-        dts = {c.dtype for c in conf_list}
-        if len(dts) != 1:
-            raise TypeError(f"mixed confidence dtypes {dts}")
-        conf = torch.cat([c.reshape(-1).cpu() for c in conf_list])
-    else:
-        conf = torch.zeros(0, dtype=torch.float16)
-    ids = {}
-    label_id = np.array([ids.setdefault(s, len(ids)) for s in labels], dtype=np.int32)
-    t = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(dev)
-    nf = len(slots)
-    inv = geom.inv_pose_host[np.array(slots, dtype=np.int64)] if nf else np.zeros((0, 16))
-    return DeviceScene(
-        scene_id=geom.scene_id, n_points=geom.n_points, nw=geom.nw, height=h, width=w, cam_intr=geom.cam_intr,
-        xyz=geom.xyz, tile_bounds=geom.tile_bounds, depth=geom.depth,
-        inv_pose=t(inv.reshape(nf, 16), torch.float64), depth_index=t(np.array(slots, np.int32), torch.int32),
-        frame_mask=t(np.array(f_mask, np.int32), torch.int32), frame_rowbase=t(np.array(f_rowbase, np.int32), torch.int32),
-        frame_nmask=t(np.array(f_nmask, np.int32), torch.int32), frame_flags=t(np.zeros(nf, np.int32), torch.int32),
-        n_frames=nf, n_mask_frames=nf, n_viewed=geom.n_viewed, word_bits=word_bits, n_rows=n_rows,
-        run_start=t(rs, torch.int32), run_end=t(re, torch.int32), mask_run_offs=t(roffs, torch.int32),
-        view_mask_offs=t(np.array(vmo, np.int32), torch.int32), conf=conf.to(dev), labels=labels,
-        label_id=t(label_id, torch.int32), n_label_ids=max(1, len(ids)), stage1=geom.stage1, unsort=geom.unsort,
-        perm=geom.perm, depth_raw=geom.depth_raw, depth_size=geom.depth_size, viewed_in=geom.viewed, geometry=geom)
+    return _class_tables(geom, frame_table(mask_2d, word_bits, geom.slot.__getitem__), word_bits, dev, shared=True)

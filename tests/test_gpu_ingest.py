@@ -360,6 +360,29 @@ def test_a_type_error_inside_a_loader_surfaces(lib):
         ing.close()
 
 
+def test_hand_written_scene_through_the_native_path(lib):
+    """The twin of test_multiclass_host.test_hand_written_scene_against_hand_written_tables: the same five-point scene
+    and the same hand-written tables (tests/hand_scene_case.py) through prepare_scene_fast and through
+    prepare_geometry_fast + prepare_class_fast; the viewed counts of the shared geometry are int32, one per point."""
+    import hand_scene_case as case
+    from beyond_fixed_forms_amd import ingest
+    cfg = case.config()
+    m32, m64 = case.masks()
+    staging = ingest.Staging()
+    for mask_2d, with_viewed, row in ((m32, True, "scene m32"), (m32, False, "scene m32 without viewed"), (m64, True, "scene m64")):
+        ds = ingest.prepare_scene_fast(case.scene(mask_2d), cfg, DEV, with_viewed=with_viewed, staging=staging)
+        torch.cuda.synchronize()
+        assert ds.xyz.is_cuda
+        case.check_tables(ds, row, None)
+    geom = ingest.prepare_geometry_fast(case.scene([]), cfg, [m32, m64], DEV, staging=staging)
+    assert geom.viewed.dtype == torch.int32 and tuple(geom.viewed.shape) == (5,)
+    class_staging = ingest.Staging()
+    for mask_2d, row in ((m32, "class m32"), (m64, "class m64")):
+        ds = ingest.prepare_class_fast(geom, mask_2d, cfg, staging=class_staging)
+        torch.cuda.synchronize()
+        case.check_tables(ds, row, geom)
+
+
 # ------------------------------------------------------------------ B. the ingestion kernels against NumPy
 def morton_codes_np(xyz):
     """30-bit Morton codes, 10 bits per axis over the bounding box, non-finite coordinates counted as 0: the arithmetic

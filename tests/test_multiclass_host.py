@@ -111,3 +111,19 @@ def test_geometry_slots_cover_the_viewed_frames():
         assert np.array_equal(geom.depth[k].numpy(), scene.depths[f].reshape(-1))
     plain = prepare_geometry(scene, cfg, list(masks.values()), device="cpu", with_viewed=False)
     assert plain.n_viewed == 0 and "5" in plain.frame_ids and set(plain.frame_ids) <= set(geom.frame_ids)
+
+
+def test_hand_written_scene_against_hand_written_tables():
+    """tests/hand_scene_case.py: the tables of a five-point scene with two mask lists, through prepare_scene (with and
+    without the viewed frames) and through prepare_geometry + prepare_class, against tables written out by hand."""
+    import hand_scene_case as case
+    from beyond_fixed_forms_amd.scene import prepare_class, prepare_geometry, prepare_scene
+    cfg = case.config()
+    m32, m64 = case.masks()
+    case.check_tables(prepare_scene(case.scene(m32), cfg, device="cpu"), "scene m32", None)
+    case.check_tables(prepare_scene(case.scene(m32), cfg, device="cpu", with_viewed=False), "scene m32 without viewed", None)
+    case.check_tables(prepare_scene(case.scene(m64), cfg, device="cpu"), "scene m64", None)
+    geom = prepare_geometry(case.scene([]), cfg, [m32, m64], device="cpu")
+    assert geom.viewed is None                            # counted on the GPU only
+    case.check_tables(prepare_class(geom, m32, cfg), "class m32", geom)
+    case.check_tables(prepare_class(geom, m64, cfg), "class m64", geom)
