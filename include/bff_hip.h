@@ -277,7 +277,11 @@ int bff_merge_adjacency(const uint64_t *rows, int32_t n_rows, int64_t nw, const 
  * chunk_pop (optional, from bff_row_stats): second-level bound -- pairs that pass the 64-bin histogram bound are
  * bounded again by sum over the shared 512-point chunks of min(points of i, points of j) before any word is read.
  * diag (optional, NULL in production): int32 [16 + 2 * capacity], zeroed by the caller: += {tile pairs evaluated,
- * chunks visited, candidate pairs, unions, phase clocks ...} (scripts/diag_merge_phases.py). */
+ * chunks visited, candidate pairs, unions, phase clocks ...} (scripts/diag_merge_phases.py).  The counters, summed
+ * over the blocks of the tile pass (a split tile pair runs one block per part, and each part counts):
+ *   [0] blocks that got past the bounds (some candidate pair left), [1] chunks on their chunk lists, [2] candidate
+ *   pairs, [3] unions pushed into the global forest, [9] blocks that took the pair-list path, [10] blocks that took
+ *   the dense 4x4 path ([9] + [10] = [0]); [4]-[8] and [11] are phase clocks, [14] / [15] select the block timeline. */
 int64_t bff_merge_scratch_words(int32_t n_rows);
 /* Whether bff_merge_components applies the chunk bound for rows of nw words (clouds of >= ~0.5 M points; the environment
  * variable BFF_CHUNK_BOUND=0/1 overrides): callers can skip computing chunk_pop otherwise. */
