@@ -23,6 +23,8 @@ _P, _I, _L, _D, _F = c_void_p, c_int32, c_int64, c_double, c_float
 SIGNATURES = {
     "bff_rle_to_maskbits": [_P, _P, _P, _P, _I, _L, _I, _P, _P, _P],
     "bff_rle_to_labels": [_P, _P, _P, _P, _I, _L, _I, _P, _P, _P, _P],
+    "bff_masks2d_count": [_P, _I, _L, _P, _P, _P],
+    "bff_masks2d_runs": [_P, _I, _L, _P, _P, _P, _P],
     "bff_project_views": [_P, _L, _L, _P, _P, _I, _P, _P, _I, _I, _D, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P],
     "bff_depth_tile_u16": [_P, _I, _I, _I, _P, _I, _P],
     "bff_project_views_u16": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P],
@@ -74,6 +76,7 @@ SIGNATURES = {
     "bff_depth_from_u16": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P],
 }
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
+         "bff_masks2d_tile_pixels": (c_int32, []),
          "bff_chunk_mask_words": (c_int32, [c_int64]), "bff_label_plane_stride": (c_int64, [c_int64]), "bff_resolve_overlaps_max_rows": (c_int32, []),
          "bff_point_tile_size": (c_int32, []), "bff_depth_tiled_texels": (c_int64, [c_int32, c_int32]), "bff_merge_scratch_words": (c_int64, [c_int32]), "bff_merge_uses_chunk_bound": (c_int32, [c_int64]),
          "bff_profile_next_merge": (c_int32, [_P, _P]), "bff_group_slice_cap": (c_int32, [c_int32, c_int32]),
@@ -82,7 +85,7 @@ PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, [
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class BffLibraryError(RuntimeError):
@@ -242,6 +245,18 @@ def rle_to_maskbits(run_start, run_end, mask_run_offs, view_mask_offs, n_views, 
     call("bff_rle_to_maskbits", _ptr(run_start, i32), _ptr(run_end, i32), _ptr(mask_run_offs, i32),
          _ptr(view_mask_offs, i32), n_views, n_pixels, word_bits,
          _ptr(maskbits, torch.int32 if word_bits == 32 else torch.int64), _ptr(segmap, i32))
+
+
+def masks2d_count(masks, bits, n_runs):
+    """Dense masks uint8 [M][P] (bool viewed as uint8) -> bit planes int64 [M][ceil(P/64)] + run counts int32 [M]
+    (bff_masks2d_count: the one pass that reads the dense bytes)."""
+    call("bff_masks2d_count", _ptr(masks, u8), masks.shape[0], masks.shape[1], _ptr(bits, i64), _ptr(n_runs, i32))
+
+
+def masks2d_runs(bits, n_pixels, run_offs, run_start, run_end):
+    """Bit planes -> run_start / run_end at the absolute positions run_offs (int32 [M + 1], device) names."""
+    call("bff_masks2d_runs", _ptr(bits, i64), bits.shape[0], n_pixels, _ptr(run_offs, i32), _ptr(run_start, i32),
+         _ptr(run_end, i32))
 
 
 def label_plane_stride(n_pixels):

@@ -51,4 +51,17 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 
 __device__ __forceinline__ int popc64(uint64_t v) { return __popcll(v); }
 
+// Run starts and ends of word w of a bit row (rows.hip: bit rows -> 1-D RLE; masks2d.hip: bit planes -> run tables).
+// A run starts at point p iff bit p is set and bit p-1 is not; it ends (exclusive) at e iff bit e-1 is set and bit e
+// is not.  Padding bits are zero and word nw is a virtual zero word, so a run reaching the last point ends like any other.
+__device__ __forceinline__ void rle_word_edges(const uint64_t *row, int64_t w, int64_t nw, uint64_t &starts,
+                                               uint64_t &ends)
+{
+    const uint64_t cur = w < nw ? row[w] : 0;
+    const uint64_t prev_bit = w ? (row[w - 1] >> 63) : 0;
+    const uint64_t shifted = (cur << 1) | prev_bit;             // bit p = value of point p-1
+    starts = cur & ~shifted;
+    ends = ~cur & shifted;
+}
+
 }  // namespace bff

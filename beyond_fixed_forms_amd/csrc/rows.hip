@@ -1905,17 +1905,7 @@ __global__ void rle_to_rows_kernel(const int32_t *__restrict__ run_start, const 
 // and bit e is not.  Padding bits are zero and one virtual zero word follows the row, so a run reaching the
 // last point ends at N like any other.  Starts and ends alternate: the k-th end closes the k-th start.
 // Pass 1 counts the starts per row; pass 2 writes counts[2k] = start+1 (1-based) and counts[2k+1] = end,
-// rank by rank (block scan of the per-word counts); pass 3 turns the ends into lengths.
-__device__ __forceinline__ void rle_word_edges(const uint64_t *row, int64_t w, int64_t nw, uint64_t &starts,
-                                               uint64_t &ends)
-{
-    const uint64_t cur = w < nw ? row[w] : 0;
-    const uint64_t prev_bit = w ? (row[w - 1] >> 63) : 0;
-    const uint64_t shifted = (cur << 1) | prev_bit;             // bit p = value of point p-1
-    starts = cur & ~shifted;
-    ends = ~cur & shifted;
-}
-
+// rank by rank (block scan of the per-word counts); pass 3 turns the ends into lengths.  rle_word_edges: common.h.
 __global__ __launch_bounds__(256) void rle_count_kernel(const uint64_t *__restrict__ rows, int64_t nw,
                                                          int32_t *__restrict__ n_runs)
 {

@@ -31,8 +31,9 @@ import torch
 
 from . import _lib
 from .scene import (DeviceScene, SceneGeometry, class_inv_poses, class_word_bits, concat_confidences, confidence_dtype,
-                    count_geometry_viewed, device_scene, frame_table, frame_union, label_ids, new_geometry, padded_points,
-                    prepare_class, prepare_geometry, prepare_scene, raw_depth_on_device, slots_on_first_use,
+                    count_geometry_viewed, device_scene, frame_table, frame_union, label_ids, masks_all_rle, new_geometry,
+                    padded_points, prepare_class, prepare_geometry, prepare_scene, raw_depth_on_device, run_tables,
+                    slots_on_first_use,
                     viewed_frame_ids, with_viewed_counts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -130,9 +131,13 @@ def pack_rles(rles, expect_length, staging: Staging, tag, n_threads=4):
     return rs[:got], re[:got], offs[:n + 1]
 
 
-def _run_tables(rles, h, w, staging, dev, n_threads):
-    """2-D RLE -> (run_start, run_end, mask_run_offs) on the device: built by native threads straight into pinned
-    staging.  None when pack_rles declines (the caller takes the exact slow path)."""
+def _run_tables(ft, h, w, staging, dev, n_threads):
+    """A frame table's masks -> (run_start, run_end, mask_run_offs) on the device.  RLE dicts: built by native threads
+    straight into pinned staging; None when pack_rles declines (the caller takes the exact slow path).  Dense masks /
+    DeviceRuns (scene.run_tables): encoded and concatenated on the device -- no native builder, no staging for runs."""
+    if not masks_all_rle(ft):
+        return run_tables(ft, h, w, dev)
+    rles = ft.rles
     if rles:
         packed = pack_rles(rles, h * w, staging, "m2d", n_threads)
         if packed is None:
@@ -226,7 +231,7 @@ def prepare_scene_fast(scene, cfg, device="cuda", with_viewed=True, staging: Sta
     slot, ids = slots_on_first_use()
     ft = frame_table(scene.mask_2d, word_bits, slot, viewed)
     lap("frame table (python)")
-    runs = _run_tables(ft.rles, int(cfg.height_2d), int(cfg.width_2d), staging, dev, n_threads)
+    runs = _run_tables(ft, int(cfg.height_2d), int(cfg.width_2d), staging, dev, n_threads)
     lap("run tables (native) + upload")
     if runs is None:
         return slow()                                # rare inputs: exact slow path
@@ -343,7 +348,7 @@ def prepare_class_fast(geom: SceneGeometry, mask_2d, cfg, staging: Staging = Non
         staging.wait()
         word_bits = class_word_bits(mask_2d)
         ft = frame_table(mask_2d, word_bits, geom.slot.__getitem__)
-        runs = _run_tables(ft.rles, geom.height, geom.width, staging, dev, n_threads)
+        runs = _run_tables(ft, geom.height, geom.width, staging, dev, n_threads)
         if runs is not None:
             ds = _class_to_device(geom, ft, word_bits, runs, staging, True)
             staging.fence()

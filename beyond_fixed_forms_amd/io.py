@@ -132,6 +132,8 @@ def load_scene(cfg, cls: str, scene_id: str, depth_on_device: bool = False, stag
     points = np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"))                         # P:387
     # the mask_2d file is the user's own upstream output (segmentation_2d.py:500-504): a pickled list of
     # dicts holding numpy count arrays, loaded exactly as the reference does (P:396)
+    # (a file written before the RLE step, RLE:101-130 -- dense (M,1,H,W) tensors -- passes through as it is:
+    # scene.run_tables encodes those on the device)
     mask_2d = torch.load(os.path.join(cfg.mask_2d_dir, cls, f"{scene_id}.pth"), weights_only=False)
     color_dir = os.path.join(scene_dir, "color")
     color_files = [f for f in os.listdir(color_dir) if f.endswith(".jpg")] if os.path.isdir(color_dir) else []

@@ -4,7 +4,8 @@ Mirrors the loading part of the reference scene loop (tools/projection_2d_to_3d.
 :422-436, :526-535): intrinsics `[:3,:3]`, cloud `[:, :3]` with a homogeneous 1, per-frame
 `np.linalg.inv(pose)` (kept on the host in float64, exactly as the reference computes it), depth
 images, and the RLE `mask_2d` list -- which is turned into flat run tables instead of being decoded
-to dense (M,1,H,W) tensors.
+to dense (M,1,H,W) tensors.  An entry's masks may also arrive dense (the 2-D stage's own tensors) or as
+masks2d.DeviceRuns (already encoded on the device); run_tables is the one place that tells them apart.
 
 prepare_scene (one mask list) and prepare_geometry + prepare_class (several lists against one resident
 scene) are put together from the same pieces: cloud_host_layout, host_depth_to_device /
@@ -237,11 +238,13 @@ class FrameTable:
     frame_nmask: List[int]
     frame_flags: List[int]
     view_mask_offs: List[int]
-    rles: list                           # every 2-D mask, in row order
+    rles: list                           # every 2-D mask that came as an RLE dict, in row order
     conf_list: list                      # one confidence tensor per mask_2d entry
     labels: List[str]
     n_rows: int
     n_mask_frames: int
+    mask_entries: list = dataclasses.field(default_factory=list)   # each entry's `segmented_frame_masks` as given: a list
+                                                                   # of RLE dicts, a dense tensor or a masks2d.DeviceRuns
 
     def int_tables(self):
         return [np.asarray(a, dtype=np.int32) for a in (self.depth_index, self.frame_mask, self.frame_rowbase,
@@ -256,7 +259,7 @@ def frame_table(mask_2d, word_bits, slot, viewed=None) -> FrameTable:
     (SceneGeometry.viewed)."""
     viewed_left = dict.fromkeys(viewed or ())        # ordered set of frames still to be counted
     frame_ids, d_idx, f_mask, f_rowbase, f_nmask, f_flags = [], [], [], [], [], []
-    all_rles, view_mask_offs, conf_list, labels = [], [0], [], []
+    all_rles, view_mask_offs, conf_list, labels, entries = [], [0], [], [], []
     row = 0
     for fr in mask_2d:
         fid = fr["frame_id"][:-4]
@@ -274,7 +277,9 @@ def frame_table(mask_2d, word_bits, slot, viewed=None) -> FrameTable:
             f_flags.append(1 if counted else 0)
             view_mask_offs.append(view_mask_offs[-1] + mc)
             row += mc
-        all_rles += rles
+        if isinstance(rles, (list, tuple)):
+            all_rles += rles
+        entries.append(rles)
         conf_list.append(fr["confidences"])
         labels += fr["labels"]
     n_mask_frames = len(frame_ids)
@@ -282,7 +287,7 @@ def frame_table(mask_2d, word_bits, slot, viewed=None) -> FrameTable:
         frame_ids.append(fid); d_idx.append(slot(fid))
         f_mask.append(-1); f_rowbase.append(0); f_nmask.append(0); f_flags.append(1)
     return FrameTable(frame_ids, d_idx, f_mask, f_rowbase, f_nmask, f_flags, view_mask_offs, all_rles, conf_list, labels,
-                      row, n_mask_frames)
+                      row, n_mask_frames, entries)
 
 
 def confidence_dtype(conf_list):
@@ -441,16 +446,111 @@ def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -
     return new_geometry(scene, h, w, n, ids, inv, n_viewed, xyz, depth3, bounds, t32(unsort), t32(perm))
 
 
-def _class_tables(geom, ft, word_bits, dev, shared) -> DeviceScene:
+def masks_all_rle(ft: FrameTable) -> bool:
+    """Does every entry of the list hold its masks as RLE dicts (the mask_2d file's form)?"""
+    return all(isinstance(e, (list, tuple)) for e in ft.mask_entries)
+
+
+def _concat_device_runs(parts, dev):
+    """DeviceRuns in row order -> (run_start, run_end, mask_run_offs) on `dev`, without a host copy of any run.
+    Consecutive views of one encode_masks call are taken together; when every stretch is a whole call's tables (what
+    run_tables and masks2d.to_device_runs make) the runs are concatenated as they are and the offsets shifted by the
+    tables' sizes.  Anything else (a subset of a call's frames) is gathered on the device, which costs one read-back of
+    the total (8 bytes)."""
+    i32 = torch.int32
+    segs = []                                   # [owner, first mask, end mask]
+    for d in parts:
+        if len(d) == 0:
+            continue
+        own = d.owner if d.owner is not None else d
+        if segs and segs[-1][0] is own and segs[-1][2] == d.first_mask:
+            segs[-1][2] += len(d)
+        else:
+            segs.append([own, d.first_mask, d.first_mask + len(d)])
+    if not segs:
+        z = torch.zeros(0, dtype=i32, device=dev)
+        return [z, z.clone(), torch.zeros(1, dtype=i32, device=dev)]
+    on = lambda t: t if t.device == dev else t.to(dev)
+    if all(a == 0 and b == own.n_masks for own, a, b in segs):
+        if len(segs) == 1:
+            own = segs[0][0]
+            return [on(own.run_start), on(own.run_end), on(own.mask_run_offs)]
+        base, offs = 0, [torch.zeros(1, dtype=i32, device=dev)]
+        for own, _, _ in segs:
+            offs.append(on(own.mask_run_offs)[1:] + base)
+            base += int(own.run_start.shape[0])
+        if base >= 1 << 31:
+            raise ValueError(f"{base} runs of 2-D masks in one scene, at most 2^31 - 1")
+        return [torch.cat([on(own.run_start) for own, _, _ in segs]), torch.cat([on(own.run_end) for own, _, _ in segs]),
+                torch.cat(offs).to(i32)]
+    lo, ln, tab, base = [], [], [], 0
+    for own, a, b in segs:
+        o = on(own.mask_run_offs).to(torch.int64)
+        lo.append(o[a:b] + base)
+        ln.append(o[a + 1:b + 1] - o[a:b])
+        tab.append(own)
+        base += int(own.run_start.shape[0])
+    lo, ln = torch.cat(lo), torch.cat(ln)
+    cum = torch.cumsum(ln, 0)
+    total = int(cum[-1].item())
+    if total >= 1 << 31:
+        raise ValueError(f"{total} runs of 2-D masks in one scene, at most 2^31 - 1")
+    src = torch.repeat_interleave(lo - (cum - ln), ln, output_size=total) + torch.arange(total, device=dev)
+    offs = torch.zeros(lo.shape[0] + 1, dtype=i32, device=dev)
+    offs[1:] = cum
+    return [torch.cat([on(t.run_start) for t in tab])[src], torch.cat([on(t.run_end) for t in tab])[src], offs]
+
+
+def run_tables(ft: FrameTable, height, width, dev):
+    """(run_start, run_end, mask_run_offs) of a frame table on `dev`, whatever form its entries' masks came in -- the
+    one place that decides:
+      all RLE dicts              runs_from_rles on the host, then uploaded (the mask_2d file's path, unchanged);
+      dense and / or DeviceRuns  the dense entries are encoded on the device (one masks2d.encode_masks call per scene)
+                                 and the tables concatenated there: no run visits the host;
+      a mixed list               the device entries are read back (DeviceRuns.to_rles) and the RLE path is taken."""
+    from . import masks2d
+    n_pixels = height * width
     for r in ft.rles:
-        if int(r["length"]) != geom.height * geom.width:
-            raise ValueError(f"mask RLE length {r['length']} != H*W = {geom.height * geom.width}")
-    runs = runs_from_rles(ft.rles, "2-D mask")
+        if int(r["length"]) != n_pixels:
+            raise ValueError(f"mask RLE length {r['length']} != H*W = {n_pixels}")
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int32).to(dev)
+    if masks_all_rle(ft):
+        return [t(a) for a in runs_from_rles(ft.rles, "2-D mask")]
+    entries = list(ft.mask_entries)
+    dense = [i for i, e in enumerate(entries) if masks2d.is_dense(e)]
+    for i in dense:
+        masks2d._dense_shape_check(entries[i], height, width)
+    for e in entries:
+        if isinstance(e, masks2d.DeviceRuns) and len(e) and e.n_pixels != n_pixels:
+            raise ValueError(f"mask RLE length {e.n_pixels} != H*W = {n_pixels}")
+        if not (isinstance(e, (list, tuple, masks2d.DeviceRuns)) or masks2d.is_dense(e)):
+            raise TypeError(f"segmented_frame_masks: RLE dicts, a dense tensor or DeviceRuns expected, got {type(e).__name__}")
+    if dev.type != "cuda":
+        raise ValueError("dense masks / DeviceRuns need a GPU device (there is no CPU encoder)")
+    if dense:
+        for i, d in zip(dense, masks2d.encode_masks([entries[i] for i in dense], dev)):
+            entries[i] = d
+    if not any(isinstance(e, (list, tuple)) and len(e) for e in entries):
+        return _concat_device_runs([e for e in entries if isinstance(e, masks2d.DeviceRuns)], dev)
+    rles, fetched = [], {}                      # every encode_masks call's tables are read back once
+    for e in entries:
+        if isinstance(e, masks2d.DeviceRuns):
+            own = e.owner if e.owner is not None else e
+            if id(own) not in fetched:
+                fetched[id(own)] = own.to_rles()
+            rles += fetched[id(own)][e.first_mask:e.first_mask + len(e)]
+        else:
+            rles += list(e)
+    return [t(a) for a in runs_from_rles(rles, "2-D mask")]
+
+
+def _class_tables(geom, ft, word_bits, dev, shared) -> DeviceScene:
+    runs = run_tables(ft, geom.height, geom.width, dev)
     conf = concat_confidences(ft.conf_list)
     label_id, n_ids = label_ids(ft.labels)
     t = lambda a, dtype=torch.int32: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(dev)
     return device_scene(geom, ft, word_bits, [t(a) for a in ft.int_tables() + [label_id]],
-                        t(class_inv_poses(geom, ft), torch.float64), [t(a) for a in runs], conf.to(dev), n_ids, shared)
+                        t(class_inv_poses(geom, ft), torch.float64), runs, conf.to(dev), n_ids, shared)
 
 
 def prepare_scene(scene, cfg, device="cuda", with_viewed=True, sort_points=True, raw_depth_resident=None) -> DeviceScene:

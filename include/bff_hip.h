@@ -32,7 +32,7 @@ extern "C" {
 #define BFF_E_ARG (-1)      /* null pointer / negative size / unsupported parameter */
 #define BFF_E_LIMIT (-2)    /* size beyond what a kernel supports (documented per call) */
 
-#define BFF_ABI_VERSION 8
+#define BFF_ABI_VERSION 9
 
 int bff_abi_version(void);
 const char *bff_last_error(void);
@@ -84,6 +84,29 @@ int64_t bff_label_plane_stride(int64_t n_pixels);
 int bff_rle_to_labels(const int32_t *run_start, const int32_t *run_end, const int32_t *mask_run_offs,
                       const int32_t *view_mask_offs, int32_t n_views, int64_t n_pixels, int32_t word_bits,
                       uint8_t *labels, void *words, uint32_t *segmap, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * a1b -- dense 2-D masks -> the run tables of a1, on the device.  Replaces RLE.rle_encode_batch (RLE:10-32: one
+ * nonzero + one host copy per mask) + encode_2d_masks (RLE:63-80) for a caller that holds the (M,1,H,W) bool tensors
+ * of SEG:276-305 on the device.  Two passes with one scan of n_runs in between (the host's: a device cumsum); the
+ * dense bytes are read once, by the first.
+ *
+ * Dense 2-D masks -> bit planes + run counts.  masks: uint8 [n_masks][n_pixels] (the layout of a contiguous
+ * torch.bool / torch.uint8 (M,1,H,W) tensor; ANY non-zero byte is a set pixel), n_pixels = H*W < 2^31.
+ * bits: uint64 [n_masks][nw], nw = ceil(n_pixels/64), bit p%64 of word p/64 = pixel p, padding bits zero
+ * (the row layout of bff_pack_rows).  n_runs: int32 [n_masks] = number of maximal runs of set pixels of each mask
+ * (written, not accumulated: the caller clears nothing).  masks needs no alignment (mask g starts at byte
+ * g * n_pixels) and no byte past masks + n_masks * n_pixels is read; bits and n_runs must not overlap masks. */
+int bff_masks2d_count(const uint8_t *masks, int32_t n_masks, int64_t n_pixels, uint64_t *bits, int32_t *n_runs, void *stream);
+/* Bit planes -> run tables in the layout bff_rle_to_maskbits reads: mask g writes its runs, ascending, as
+ * run_start[k] / run_end[k] (0-based, end exclusive) for k in [run_offs[g], run_offs[g+1]).  run_offs: int32
+ * [n_masks + 1] on the device, absolute positions in the caller's tables (so frames append into one table);
+ * run_offs[g+1] - run_offs[g] must be the mask's n_runs (nothing is written outside those slots whatever it is).
+ * run_start / run_end may be NULL when no mask has a run. */
+int bff_masks2d_runs(const uint64_t *bits, int32_t n_masks, int64_t n_pixels, const int32_t *run_offs,
+                     int32_t *run_start, int32_t *run_end, void *stream);
+/* Pixels of one mask a block of the count pass reads (the tile of its grid; tests put sizes around it). */
+int32_t bff_masks2d_tile_pixels(void);
 
 /* ------------------------------------------------------------------------------------------
  * a2-a7 (+a15) -- fused per-frame: world->camera transform, projection, rounding, bounds +
