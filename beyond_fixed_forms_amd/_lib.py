@@ -30,6 +30,7 @@ SIGNATURES = {
     "bff_project_views_u16": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P],
     "bff_point_tile_bounds": [_P, _L, _L, _P, _P],
     "bff_count_viewed": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _I, _P, _P, _P],
+    "bff_render_depth_u16": [_P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "bff_popcount_rows": [_P, _P, _I, _L, _P, _P],
     "bff_cross_popcount": [_P, _P, _I, _P, _P, _I, _L, _P, _P],
     "bff_row_stats": [_P, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P],
@@ -85,7 +86,7 @@ PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, [
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class BffLibraryError(RuntimeError):
@@ -316,6 +317,31 @@ def count_viewed(xyz_soa, n_points, inv_pose, cam_intr, depth, depth_index, heig
     call("bff_count_viewed", _ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(inv_pose, f64), ctypes.cast(k, c_void_p),
          inv_pose.shape[0], _ptr(depth), int(hs), int(ws), layout, _ptr(depth_index, i32), height, width,
          float(depth_thresh), int(frames_per_block), _ptr(viewed_count, i32), _ptr(tile_bounds, f64))
+
+
+RENDER_SCRATCH_TEXELS = 1 << 26     # texels of the renderer's uint32 scratch (256 MB): more frames than fit are rendered in runs
+
+
+def render_depth(xyz_soa, n_points, inv_pose, cam_intr, height, width, depth_h, depth_w, tile_bounds=None,
+                 frames_per_block=0, scratch_texels=None):
+    """Depth frames out of the cloud itself (bff_render_depth_u16): every point of `xyz_soa` that projects in bounds and
+    in front of the camera of frame f (inv_pose f64 [F][16], device) splats rint(z * 1000) into texel (v * depth_h //
+    height, u * depth_w // width) of frame f, a texel keeps the minimum, 0 = no point.  -> int16 [F][depth_h][depth_w] (the
+    uint16 millimetres, as the decoded depth PNGs are held), on the current launch stream.  The call needs a uint32
+    scratch texel per result texel: at most scratch_texels (default RENDER_SCRATCH_TEXELS) are allocated, and the frames
+    are rendered in runs of as many as fit (each run reads the cloud once more).  frames_per_block: the kernel's frame
+    tile, 0 = the library's choice."""
+    k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
+    f, plane = int(inv_pose.shape[0]), int(depth_h) * int(depth_w)
+    out = torch.empty((f, int(depth_h), int(depth_w)), dtype=torch.int16, device=xyz_soa.device)
+    per = max(1, min(f, (RENDER_SCRATCH_TEXELS if scratch_texels is None else int(scratch_texels)) // max(plane, 1)))
+    scratch = torch.empty(max(per * plane, 1), dtype=i32, device=xyz_soa.device)
+    for f0 in range(0, max(f, 1), per):
+        f1 = min(f, f0 + per)
+        call("bff_render_depth_u16", _ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(inv_pose[f0:f1], f64),
+             ctypes.cast(k, c_void_p), f1 - f0, int(height), int(width), int(depth_h), int(depth_w), int(frames_per_block),
+             _ptr(scratch), _ptr(out[f0:f1]), _ptr(tile_bounds, f64))
+    return out
 
 
 def tile_depth(raw, metres=True):

@@ -16,6 +16,10 @@ DEFAULTS = dict(
     if_detected_ratio_threshold=True, detected_ratio_threshold=0.38,
     remove_filtered_masks=0.4, remove_small_masks=5,
     stage1_iou_thres=0.1, refinment_sim_percentile=0.2, refiment_iou_thres=0.45,
+    # not a key of the reference: integer stride s >= 1 renders the depth frames from the cloud at (ceil(height_2d / s),
+    # ceil(width_2d / s)) instead of reading depth/<frame>.png (scene.rendered_depth_on_device); 0 = off.  8 is a starting
+    # value nobody has tuned
+    depth_from_cloud=0,
 )
 
 

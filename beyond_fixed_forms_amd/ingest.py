@@ -31,9 +31,9 @@ import torch
 
 from . import _lib
 from .scene import (DeviceScene, SceneGeometry, class_inv_poses, class_word_bits, concat_confidences, confidence_dtype,
-                    count_geometry_viewed, device_scene, frame_table, frame_union, label_ids, masks_all_rle, new_geometry,
-                    padded_points, prepare_class, prepare_geometry, prepare_scene, raw_depth_on_device, run_tables,
-                    slots_on_first_use,
+                    count_geometry_viewed, depth_from_cloud_stride, device_scene, frame_table, frame_union, label_ids,
+                    masks_all_rle, new_geometry, padded_points, prepare_class, prepare_geometry, prepare_scene,
+                    raw_depth_on_device, rendered_depth_on_device, run_tables, slots_on_first_use,
                     viewed_frame_ids, with_viewed_counts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -194,6 +194,14 @@ def _geometry_to_device(scene, cfg, ids, n_viewed, dev, staging, n_threads, lap=
     inv = np.linalg.inv(np.stack([np.asarray(scene.poses[f], dtype=np.float64) for f in ids])).reshape(len(ids), 16) \
         if ids else np.zeros((0, 16))
     lap("pose inverses")
+    stride = depth_from_cloud_stride(cfg)
+    if stride:                                       # no depth frames: rendered from the cloud, so the cloud goes first
+        xyz, unsort, perm, bounds = _cloud_to_device(pts, dev, staging)
+        lap("cloud (copy to pinned, enqueue, layout)")
+        depth3 = _depth_to_device(scene, ids, pts.shape[0], h, w, dev, staging, n_threads,
+                                  cloud=(xyz, inv, scene.cam_intr, stride, bounds))
+        lap("depth (rendered from the cloud)")
+        return new_geometry(scene, h, w, pts.shape[0], ids, inv, n_viewed, xyz, depth3, bounds, unsort, perm)
     depth3 = _depth_to_device(scene, ids, pts.shape[0], h, w, dev, staging, n_threads)
     if depth3 is None:
         return None
@@ -244,10 +252,21 @@ def prepare_scene_fast(scene, cfg, device="cuda", with_viewed=True, staging: Sta
     return ds
 
 
-def _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads):
+def _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads, cloud=None):
     """The frames `depth_ids` of a scene on the device, in that order (scene.host_depth_to_device's layout rules): packed
     into pinned staging by native threads and uploaded as ONE asynchronous copy.  -> (depth, depth_raw, depth_size), or
-    None when the frames are of mixed sizes / dtypes (the caller takes the exact slow path)."""
+    None when the frames are of mixed sizes / dtypes (the caller takes the exact slow path).
+    cloud = (xyz, the frames' inverse poses on the host, K, stride, tile bounds): the scene has no depth frames (config key
+    depth_from_cloud); they are rendered from the cloud already laid out on the device, on the current stream
+    (scene.rendered_depth_on_device) -- no staging is taken and nothing crosses the bus but the poses."""
+    if cloud is not None:
+        xyz, inv, cam_intr, stride, bounds = cloud
+        inv_dev = None
+        if inv.size:
+            pstage = staging.get("render.poses", inv.nbytes)
+            pstage.numpy()[:inv.nbytes].view(np.float64)[:] = inv.reshape(-1)
+            inv_dev = pstage[:inv.nbytes].view(torch.float64).view(-1, 16).to(dev, non_blocking=True)
+        return rendered_depth_on_device(xyz, n, inv, cam_intr, h, w, stride, bounds, inv_pose_dev=inv_dev)
     raw_depth = getattr(scene, "depths_raw", None)
     src = raw_depth if raw_depth is not None else scene.depths
     frames = [src[f] for f in depth_ids]

@@ -368,6 +368,41 @@ def host_depth_to_device(scene, ids, n_points, h, w, dev, raw_depth_resident=Non
     return (out, None, None) if raw is None else raw_depth_on_device(out, n_points, h, w, raw_depth_resident)
 
 
+def depth_from_cloud_stride(cfg) -> int:
+    """The optional config key `depth_from_cloud`: 0 (or absent) = the scene brings its depth frames; an integer stride
+    s >= 1 = they are rendered from the cloud at (ceil(height_2d / s), ceil(width_2d / s))."""
+    v = cfg.get("depth_from_cloud", 0)
+    if v is None or v is False:
+        return 0
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+        raise ValueError(f"depth_from_cloud: a non-negative integer stride expected, got {v!r}")
+    return int(v)
+
+
+def rendered_depth_size(h, w, stride):
+    return -(-h // stride), -(-w // stride)
+
+
+def rendered_depth_on_device(xyz, n_points, inv_pose_host, cam_intr, h, w, stride, tile_bounds=None,
+                             raw_depth_resident=None, inv_pose_dev=None):
+    """host_depth_to_device for a scene without depth frames: one frame per row of inv_pose_host (the slots' inverse
+    poses, f64 [slots][16]) rendered from the sorted cloud `xyz` on its device (bff_render_depth_u16, one call for all
+    slots, on the current stream) at 1 / stride of the working resolution, handed to raw_depth_on_device like the PNGs'
+    uint16 frames -> (depth, depth_raw, depth_size).  inv_pose_dev: the same poses already on the device (ingest.py
+    sends them through its pinned staging)."""
+    from . import _lib
+    dev = xyz.device
+    if dev.type != "cuda":
+        raise ValueError("depth_from_cloud needs a GPU device (there is no CPU renderer)")
+    if not len(inv_pose_host):
+        return torch.zeros((0, h * w), dtype=torch.float32, device=dev), None, None
+    dh, dw = rendered_depth_size(h, w, stride)
+    inv = inv_pose_dev if inv_pose_dev is not None else \
+        torch.as_tensor(np.ascontiguousarray(inv_pose_host, dtype=np.float64).reshape(-1, 16)).to(dev)
+    raw = _lib.render_depth(xyz, n_points, inv, np.asarray(cam_intr, dtype=np.float64)[:3, :3], h, w, dh, dw, tile_bounds)
+    return raw_depth_on_device(raw, n_points, h, w, raw_depth_resident)
+
+
 @dataclasses.dataclass
 class SceneGeometry:
     """The part of a resident scene that no mask touches: sorted cloud, one inverse pose and one depth slot per frame
@@ -436,12 +471,16 @@ def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -
     soa, perm, unsort, n, _ = cloud_host_layout(scene.points, sort_points)
     inv = np.stack([np.linalg.inv(np.asarray(scene.poses[f], dtype=np.float64)).reshape(16) for f in ids]) if ids \
         else np.zeros((0, 16))                                                      # :425
-    depth3 = host_depth_to_device(scene, ids, n, h, w, dev, raw_depth_resident)
+    stride = depth_from_cloud_stride(cfg)
+    if not stride:
+        depth3 = host_depth_to_device(scene, ids, n, h, w, dev, raw_depth_resident)
     xyz = torch.as_tensor(soa).to(dev)
     bounds = None
     if dev.type == "cuda" and n:
         from . import _lib
         bounds = _lib.point_tile_bounds(xyz, n)          # built once per scene, next to the spatial sort it relies on
+    if stride:                                           # no depth frames: the cloud itself says what each camera sees
+        depth3 = rendered_depth_on_device(xyz, n, inv, scene.cam_intr, h, w, stride, bounds, raw_depth_resident)
     t32 = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
     return new_geometry(scene, h, w, n, ids, inv, n_viewed, xyz, depth3, bounds, t32(unsort), t32(perm))
 

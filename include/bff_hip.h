@@ -32,7 +32,7 @@ extern "C" {
 #define BFF_E_ARG (-1)      /* null pointer / negative size / unsupported parameter */
 #define BFF_E_LIMIT (-2)    /* size beyond what a kernel supports (documented per call) */
 
-#define BFF_ABI_VERSION 9
+#define BFF_ABI_VERSION 10
 
 int bff_abi_version(void);
 const char *bff_last_error(void);
@@ -194,6 +194,32 @@ int bff_count_viewed(const double *xyz, int64_t n_points, int64_t n_pad, const d
                      const double *cam_intr_host, int32_t n_frames, const void *depth, int32_t depth_h, int32_t depth_w,
                      int32_t depth_layout, const int32_t *depth_index, int32_t height, int32_t width, double depth_thresh,
                      int32_t frames_per_block, int32_t *viewed_count, const double *tile_bounds, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Depth frames rendered from the cloud: a point z-buffer for scenes that come without a depth image per frame (posed
+ * colour captures with a reconstructed cloud).  It supplies the `depth` operand of the visibility test (P:51-70) that
+ * P:431-436 otherwise reads from depth/<frame>.png.  out_u16: uint16 [n_frames][depth_h][depth_w] row-major millimetres,
+ * 0 = no depth -- the frames bff_depth_tile_u16, bff_depth_from_u16 and bff_project_views_u16 (depth_layout 0) take.
+ * For frame f and every point n < n_points (points at n >= n_points are never read as points):
+ *   c, p, u = rint(p_0 / c_2), v = rint(p_1 / c_2) by the arithmetic contract of bff_project_views (fma chains from +0.0,
+ *   IEEE division, round half to even; in bounds iff 0 <= u < width and 0 <= v < height on the doubles, so NaN, inf and
+ *   huge values fail);
+ *   the point splats iff it is in bounds, c_2 > 0 (a surface the camera sees lies in front of it -- the sweep has no such
+ *   test) and m = rint(c_2 * 1000.0) (float64 product, half to even) satisfies 1 <= m <= 65535;
+ *   its texel is tx = (u * depth_w) / width, ty = (v * depth_h) / height in integer arithmetic on the integer pixel;
+ *   out[f][ty][tx] = the minimum m over the points that splat there, 0 if there is none.
+ * A minimum of integers does not depend on the order of its operands: the frames are the same bytes on every run and
+ * equal a sequential evaluation.  scratch_u32: uint32 [n_frames][depth_h * depth_w], set to all ones by the call itself,
+ * which the points lower with returnless unsigned atomic minima; a second kernel narrows it to out_u16.
+ *   xyz, inv_pose, cam_intr_host, tile_bounds   as bff_project_views (tile_bounds: exact frustum culling, same frames
+ *                                               with and without it)
+ *   frames_per_block  frames one block visits (its frame tile, as bff_count_viewed's); 0 = the library's choice.  The
+ *                frames do not depend on it
+ * Limits: height * width, depth_h * depth_w, height * depth_h and width * depth_w < 2^31; n_frames <= 65535. */
+int bff_render_depth_u16(const double *xyz, int64_t n_points, int64_t n_pad, const double *inv_pose,
+                         const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width,
+                         int32_t depth_h, int32_t depth_w, int32_t frames_per_block, uint32_t *scratch_u32,
+                         uint16_t *out_u16, const double *tile_bounds, void *stream);
 
 /* Frustum culling for bff_project_views (optional, exact).  bounds: float64 [ceil(n_points / bff_point_tile_size())][6]
  * = (xmin, ymin, zmin, xmax, ymax, zmax) of every tile of bff_point_tile_size() consecutive points -- the points
