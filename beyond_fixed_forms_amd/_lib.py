@@ -31,6 +31,7 @@ SIGNATURES = {
     "bff_point_tile_bounds": [_P, _L, _L, _P, _P],
     "bff_count_viewed": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _I, _P, _P, _P],
     "bff_render_depth_u16": [_P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "bff_render_mesh_depth_u16": [_P, _L, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "bff_popcount_rows": [_P, _P, _I, _L, _P, _P],
     "bff_cross_popcount": [_P, _P, _I, _P, _P, _I, _L, _P, _P],
     "bff_row_stats": [_P, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P],
@@ -79,14 +80,14 @@ SIGNATURES = {
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
          "bff_masks2d_tile_pixels": (c_int32, []),
          "bff_chunk_mask_words": (c_int32, [c_int64]), "bff_label_plane_stride": (c_int64, [c_int64]), "bff_resolve_overlaps_max_rows": (c_int32, []),
-         "bff_point_tile_size": (c_int32, []), "bff_depth_tiled_texels": (c_int64, [c_int32, c_int32]), "bff_merge_scratch_words": (c_int64, [c_int32]), "bff_merge_uses_chunk_bound": (c_int32, [c_int64]),
+         "bff_point_tile_size": (c_int32, []), "bff_mesh_lane_box": (c_int32, []), "bff_depth_tiled_texels": (c_int64, [c_int32, c_int32]), "bff_merge_scratch_words": (c_int64, [c_int32]), "bff_merge_uses_chunk_bound": (c_int32, [c_int64]),
          "bff_profile_next_merge": (c_int32, [_P, _P]), "bff_group_slice_cap": (c_int32, [c_int32, c_int32]),
          "bff_point_threshold_scratch_words": (c_int64, [c_int64]), "bff_point_threshold_capacity": (c_int32, []), "bff_point_threshold_capacity_set": (c_int32, [c_int32]), "bff_scene_header_words": (c_int32, [c_int32, c_int32]), "bff_scene_struct_bytes": (c_int32, [c_int32]),
          "bff_host_component_csr": (c_int32, [_P, _P, _I, _I, _P, _P, _P, _P]),
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class BffLibraryError(RuntimeError):
@@ -341,6 +342,28 @@ def render_depth(xyz_soa, n_points, inv_pose, cam_intr, height, width, depth_h, 
         call("bff_render_depth_u16", _ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(inv_pose[f0:f1], f64),
              ctypes.cast(k, c_void_p), f1 - f0, int(height), int(width), int(depth_h), int(depth_w), int(frames_per_block),
              _ptr(scratch), _ptr(out[f0:f1]), _ptr(tile_bounds, f64))
+    return out
+
+
+def render_mesh_depth(vertices_soa, n_vertices, faces, inv_pose, cam_intr, height, width, depth_h, depth_w,
+                      frames_per_block=0, scratch_texels=None):
+    """Depth frames out of a triangle mesh (bff_render_mesh_depth_u16): vertices_soa f64 [3][nv_pad], faces int32 [T][3]
+    on the same device with every index in [0, n_vertices) (validated by the caller: scene.checked_faces).  A texel of
+    frame f holds the nearest covering triangle's interpolated depth in millimetres at the texel's sample point, 0 =
+    none (the definition is the header's).  -> int16 [F][depth_h][depth_w], on the current launch stream.  Scratch cap
+    and frame runs are render_depth's (each run reads the mesh once more)."""
+    if faces.dtype != i32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise ValueError("render_mesh_depth: faces must be a contiguous int32 [T][3] tensor")
+    k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
+    f, plane = int(inv_pose.shape[0]), int(depth_h) * int(depth_w)
+    out = torch.empty((f, int(depth_h), int(depth_w)), dtype=torch.int16, device=vertices_soa.device)
+    per = max(1, min(f, (RENDER_SCRATCH_TEXELS if scratch_texels is None else int(scratch_texels)) // max(plane, 1)))
+    scratch = torch.empty(max(per * plane, 1), dtype=i32, device=vertices_soa.device)
+    for f0 in range(0, max(f, 1), per):
+        f1 = min(f, f0 + per)
+        call("bff_render_mesh_depth_u16", _ptr(vertices_soa, f64), int(n_vertices), vertices_soa.shape[1], _ptr(faces),
+             int(faces.shape[0]), _ptr(inv_pose[f0:f1], f64), ctypes.cast(k, c_void_p), f1 - f0, int(height), int(width),
+             int(depth_h), int(depth_w), int(frames_per_block), _ptr(scratch), _ptr(out[f0:f1]))
     return out
 
 

@@ -20,6 +20,10 @@ DEFAULTS = dict(
     # ceil(width_2d / s)) instead of reading depth/<frame>.png (scene.rendered_depth_on_device); 0 = off.  8 is a starting
     # value nobody has tuned
     depth_from_cloud=0,
+    # likewise not a key of the reference: the same stride, the frames rasterised from the scene's triangle mesh
+    # (scene_mesh_dir/<scene_id>.npz: `faces` (T, 3) integers, optionally `vertices` (V, 3); without them the faces index the
+    # rows of <scene_id>.npy).  0 = off; setting both keys is an error
+    depth_from_mesh=0, scene_mesh_dir=None,
 )
 
 

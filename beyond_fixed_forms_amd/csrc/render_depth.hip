@@ -12,6 +12,8 @@
 // Kernel shape: viewed_count_kernel's (project.hip): 256 threads own 1024 consecutive points, 4 per thread in registers
 // across the frames of the block's frame tile, poses wave-uniform, the tile culled against tile_bounds in groups of 8
 // frames.  A minimum of integers does not depend on the order of its operands: the frames are the same bytes on every run.
+// Further down: the same frames rasterised from a triangle mesh (bff_render_mesh_depth_u16), through the same scratch and
+// the same narrowing kernel.
 #include "geom.h"
 
 namespace bff {
@@ -100,6 +102,153 @@ __global__ __launch_bounds__(256) void render_depth_narrow_kernel(const uint32_t
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Depth frames rendered from a triangle mesh (include/bff_hip.h: bff_render_mesh_depth_u16).  One thread owns one triangle:
+// its nine vertex doubles stay in registers across the frames of the block's frame tile (blockIdx.y, poses wave-uniform).
+// Per frame the three vertices are transformed (camera_point), the triangle's texel box is clipped to the frame, and the
+// box's texels are tested with the header's edge functions; a covered texel takes one returnless atomicMin.  A box of
+// at most kRmLaneBox texels is walked by the lane that owns the triangle; a larger one (a triangle near the camera can
+// cover a frame) by the whole wave: ballot, broadcast of the triangle, 64 lanes stride over the box.
+//   faces    i32 [n_faces][3]    launched sorted by their smallest vertex, so that a wave's gathers are neighbours
+//   scratch, out                 as the point renderer's; the narrowing kernel is the same
+constexpr int kRmBlock = 256;
+constexpr int kRmLaneBox = 64;                                     // texels a lane walks alone; beyond: the wave path
+constexpr double kRmPixelLimit = 16777216.0;                       // 2^24: |px|, |py| of a triangle that takes part
+
+struct ScreenTri { double x0, y0, r0, x1, y1, r1, x2, y2, r2; };   // pixel position and 1 / depth of the three vertices
+struct TexelBox { int j0, i0, bw, count; };                        // first column, first row, width, texels (0 = empty)
+
+// World point -> camera depth c2 and screen position in pixels (pixel centres at integers).  c: camera_pixel's fma
+// chains, so c2 is the depth the visibility test compares; px, py: plain products and sums in the header's order.
+__device__ __forceinline__ void camera_point(const double *__restrict__ P, const CameraK &K, double x, double y, double z,
+                                             double &c2, double &px, double &py)
+{
+    const double c0 = fma(P[3], 1.0, fma(P[2], z, fma(P[1], y, fma(P[0], x, 0.0))));
+    const double c1 = fma(P[7], 1.0, fma(P[6], z, fma(P[5], y, fma(P[4], x, 0.0))));
+    c2 = fma(P[11], 1.0, fma(P[10], z, fma(P[9], y, fma(P[8], x, 0.0))));
+    px = __dadd_rn(__dadd_rn(__dmul_rn(K.k[0], c0), __dmul_rn(K.k[1], c1)), __dmul_rn(K.k[2], c2)) / c2;
+    py = __dadd_rn(__dadd_rn(__dmul_rn(K.k[3], c0), __dmul_rn(K.k[4], c1)), __dmul_rn(K.k[5], c2)) / c2;
+}
+
+// One texel against one triangle: the header's coverage test and depth; splats when covered and in range
+__device__ __forceinline__ void mesh_texel(const ScreenTri &t, int i, int j, double sx, double sy, int dw,
+                                           uint32_t *__restrict__ img)
+{
+    const double X = __dsub_rn(__dmul_rn((double)j + 0.5, sx), 0.5), Y = __dsub_rn(__dmul_rn((double)i + 0.5, sy), 0.5);
+    const double ax = t.x0 - X, ay = t.y0 - Y, bx = t.x1 - X, by = t.y1 - Y, cx = t.x2 - X, cy = t.y2 - Y;
+    const double e0 = __dsub_rn(__dmul_rn(bx, cy), __dmul_rn(cx, by));
+    const double e1 = __dsub_rn(__dmul_rn(cx, ay), __dmul_rn(ax, cy));
+    const double e2 = __dsub_rn(__dmul_rn(ax, by), __dmul_rn(bx, ay));
+    const double S = __dadd_rn(__dadd_rn(e0, e1), e2);
+    const bool covered = (S != 0.0) && ((e0 >= 0.0 && e1 >= 0.0 && e2 >= 0.0) || (e0 <= 0.0 && e1 <= 0.0 && e2 <= 0.0));
+    if (!covered) return;
+    const double z = S / __dadd_rn(__dadd_rn(__dmul_rn(e0, t.r0), __dmul_rn(e1, t.r1)), __dmul_rn(e2, t.r2));
+    const double m = rint(__dmul_rn(z, 1000.0));
+    if (m >= 1.0 && m <= 65535.0) atomicMin(img + (i * dw + j), (uint32_t)m);          // result unused: returnless
+}
+
+// Texels whose sample point can lie inside [lo, hi] along one axis (sample of texel t: (t + 0.5) * s - 0.5), one texel
+// wider at either end and clipped to [0, n): -> first, last (first > last = none).  |lo|, |hi| < 2^24 and s >= 2^-31, so
+// the quotients stay below 2^56 and their rounding error far below the texel added at either end.
+__device__ __forceinline__ void texel_range(double lo, double hi, double s, int n, int &first, int &last)
+{
+    const double a = fmax(floor((lo + 0.5) / s - 0.5) - 1.0, 0.0);
+    const double b = fmin(ceil((hi + 0.5) / s - 0.5) + 1.0, (double)(n - 1));
+    first = 0, last = -1;
+    if (a <= b) first = (int)a, last = (int)b;                      // 0 <= a <= b <= n - 1: the conversions are exact
+}
+
+__global__ __launch_bounds__(kRmBlock) void render_mesh_depth_kernel(
+    const double *__restrict__ vtx, int64_t n_vertices, int64_t nv_pad, const int32_t *__restrict__ faces, int64_t n_faces,
+    const double *__restrict__ inv_pose, CameraK K, int n_frames, int frames_per_block, int H, int W, int dh, int dw,
+    uint32_t *__restrict__ scratch)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t tri = (int64_t)blockIdx.x * kRmBlock + threadIdx.x;
+    const int f0 = blockIdx.y * frames_per_block;
+    const int f1 = min(n_frames, f0 + frames_per_block);
+    const int64_t plane = (int64_t)dh * dw;
+    const double sx = (double)W / (double)dw, sy = (double)H / (double)dh;
+
+    // the caller has validated the indices; a triangle that names a vertex outside the array is still never read
+    bool valid = tri < n_faces;
+    int64_t v0 = 0, v1 = 0, v2 = 0;
+    if (valid) {
+        v0 = faces[3 * tri], v1 = faces[3 * tri + 1], v2 = faces[3 * tri + 2];
+        valid = v0 >= 0 && v0 < n_vertices && v1 >= 0 && v1 < n_vertices && v2 >= 0 && v2 < n_vertices;
+        if (!valid) v0 = v1 = v2 = 0;
+    }
+    const double ax = vtx[v0], ay = vtx[nv_pad + v0], az = vtx[2 * nv_pad + v0];
+    const double bx = vtx[v1], by = vtx[nv_pad + v1], bz = vtx[2 * nv_pad + v1];
+    const double cx = vtx[v2], cy = vtx[nv_pad + v2], cz = vtx[2 * nv_pad + v2];
+
+    for (int f = f0; f < f1; ++f) {                                // wave-uniform
+        const double *P = inv_pose + 16 * (int64_t)f;
+        uint32_t *img = scratch + (int64_t)f * plane;
+        ScreenTri t;
+        double d0, d1, d2;
+        camera_point(P, K, ax, ay, az, d0, t.x0, t.y0);
+        camera_point(P, K, bx, by, bz, d1, t.x1, t.y1);
+        camera_point(P, K, cx, cy, cz, d2, t.x2, t.y2);
+        t.r0 = 1.0 / d0, t.r1 = 1.0 / d1, t.r2 = 1.0 / d2;
+        // comparisons on the doubles: NaN fails; a triangle that crosses the camera plane is dropped, not clipped
+        const bool takes = valid && d0 > 0.0 && d1 > 0.0 && d2 > 0.0 &&
+                           fabs(t.x0) < kRmPixelLimit && fabs(t.x1) < kRmPixelLimit && fabs(t.x2) < kRmPixelLimit &&
+                           fabs(t.y0) < kRmPixelLimit && fabs(t.y1) < kRmPixelLimit && fabs(t.y2) < kRmPixelLimit;
+        TexelBox b = {0, 0, 0, 0};
+        // two vertices at one position: e0 + e1 + e2 is exactly 0 at every texel (one e is x * y - x * y, the other two
+        // are each other's negatives), so nothing is covered
+        const bool flat = (t.x0 == t.x1 && t.y0 == t.y1) || (t.x1 == t.x2 && t.y1 == t.y2) || (t.x0 == t.x2 && t.y0 == t.y2);
+        if (takes && !flat) {
+            const double xlo = fmin(t.x0, fmin(t.x1, t.x2)), xhi = fmax(t.x0, fmax(t.x1, t.x2));
+            const double ylo = fmin(t.y0, fmin(t.y1, t.y2)), yhi = fmax(t.y0, fmax(t.y1, t.y2));
+            int j1, i1;
+            texel_range(xlo, xhi, sx, dw, b.j0, j1);
+            texel_range(ylo, yhi, sy, dh, b.i0, i1);
+            // The box must hold every texel the header's arithmetic covers.  A texel outside it lies more than a texel
+            // beyond the vertices along x (or y): x_k - X has one sign for all k, the sample point is outside the
+            // triangle, and the negative edge functions add up to at least |A| * sx / ex (A: twice the area, ex >= |x_k -
+            // X|).  Rounding can lift an edge function to >= 0 only from above -2^-52 ex ey, so the texel can pass as
+            // covered only where |A| <= 2^-51 ex ey (ex / sx); with the rounding of A itself, 2^-49 ex ey max(ex / sx, ey /
+            // sy) bounds it.  Such a sliver (three distinct vertices on a line) takes the whole frame as its box.
+            const double ex = fmax(fabs(xlo), fabs(xhi)) + (double)W, ey = fmax(fabs(ylo), fabs(yhi)) + (double)H;
+            const double A = (t.x1 - t.x0) * (t.y2 - t.y0) - (t.x2 - t.x0) * (t.y1 - t.y0);
+            if (!(fabs(A) > 0x1p-49 * ex * ey * fmax(ex / sx, ey / sy)))
+                b.j0 = 0, j1 = dw - 1, b.i0 = 0, i1 = dh - 1;
+            if (j1 >= b.j0 && i1 >= b.i0) {
+                b.bw = j1 - b.j0 + 1;
+                b.count = b.bw * (i1 - b.i0 + 1);                  // <= dh * dw < 2^31
+            }
+        }
+        if (b.count > 0 && b.count <= kRmLaneBox)                  // the lane's own walk, row by row
+            for (int k = 0, i = b.i0, j = b.j0; k < b.count; ++k) {
+                mesh_texel(t, i, j, sx, sy, dw, img);
+                if (++j == b.j0 + b.bw) j = b.j0, ++i;
+            }
+        uint64_t big = __ballot(b.count > kRmLaneBox);             // every lane of the wave is here: no early exit above
+        while (big) {
+            const int src = __ffsll((unsigned long long)big) - 1;
+            big &= big - 1;
+            ScreenTri w;
+            w.x0 = __shfl(t.x0, src), w.y0 = __shfl(t.y0, src), w.r0 = __shfl(t.r0, src);
+            w.x1 = __shfl(t.x1, src), w.y1 = __shfl(t.y1, src), w.r1 = __shfl(t.r1, src);
+            w.x2 = __shfl(t.x2, src), w.y2 = __shfl(t.y2, src), w.r2 = __shfl(t.r2, src);
+            const int wj0 = __shfl(b.j0, src), wi0 = __shfl(b.i0, src), wbw = __shfl(b.bw, src), wcount = __shfl(b.count, src);
+            for (unsigned k = lane; k < (unsigned)wcount; k += kWave)           // unsigned: wcount + 63 may pass 2^31
+                mesh_texel(w, wi0 + (int)(k / (unsigned)wbw), wj0 + (int)(k % (unsigned)wbw), sx, sy, dw, img);
+        }
+    }
+}
+
+// the scratch of a render call -> its uint16 frames
+static int narrow_frames(const uint32_t *scratch_u32, int64_t total, uint16_t *out_u16, hipStream_t st, const char *what)
+{
+    const int64_t n_narrow = ceil_div(ceil_div(total, 4), 256);
+    const int vec_ok = (reinterpret_cast<uintptr_t>(scratch_u32) % 16 == 0) && (reinterpret_cast<uintptr_t>(out_u16) % 8 == 0);
+    render_depth_narrow_kernel<<<(unsigned)n_narrow, 256, 0, st>>>(scratch_u32, total, vec_ok, out_u16);
+    return launched(what);
+}
+
 }  // namespace bff
 
 using namespace bff;
@@ -146,7 +295,50 @@ extern "C" int bff_render_depth_u16(const double *xyz, int64_t n_points, int64_t
                                                    depth_w, scratch_u32, tile_bounds);
     int rc = launched("bff_render_depth_u16");
     if (rc != BFF_OK) return rc;
-    const int vec_ok = (reinterpret_cast<uintptr_t>(scratch_u32) % 16 == 0) && (reinterpret_cast<uintptr_t>(out_u16) % 8 == 0);
-    render_depth_narrow_kernel<<<(unsigned)n_narrow, 256, 0, st>>>(scratch_u32, total, vec_ok, out_u16);
-    return launched("bff_render_depth_u16");
+    return narrow_frames(scratch_u32, total, out_u16, st, "bff_render_depth_u16");
+}
+
+extern "C" int bff_mesh_lane_box(void) { return kRmLaneBox; }
+
+extern "C" int bff_render_mesh_depth_u16(const double *vertices, int64_t n_vertices, int64_t nv_pad, const int32_t *faces,
+                                         int64_t n_faces, const double *inv_pose, const double *cam_intr_host,
+                                         int32_t n_frames, int32_t height, int32_t width, int32_t depth_h, int32_t depth_w,
+                                         int32_t frames_per_block, uint32_t *scratch_u32, uint16_t *out_u16, void *stream)
+{
+    BFF_REQUIRE(n_vertices >= 0 && nv_pad >= n_vertices && n_faces >= 0 && n_frames >= 0 && frames_per_block >= 0,
+                "bff_render_mesh_depth_u16: bad sizes");
+    BFF_REQUIRE(height > 0 && width > 0 && depth_h > 0 && depth_w > 0, "bff_render_mesh_depth_u16: bad image size");
+    BFF_LIMIT((int64_t)height * width < (1ll << 31), "bff_render_mesh_depth_u16: image larger than 2^31 pixels");
+    BFF_LIMIT((int64_t)depth_h * depth_w < (1ll << 31), "bff_render_mesh_depth_u16: depth frame larger than 2^31 texels");
+    BFF_LIMIT((int64_t)height * depth_h < (1ll << 31) && (int64_t)width * depth_w < (1ll << 31),
+              "bff_render_mesh_depth_u16: pixel x texel products beyond 2^31 (height * depth_h, width * depth_w)");
+    BFF_LIMIT(n_frames <= 65535, "bff_render_mesh_depth_u16: too many frames");
+    BFF_LIMIT(n_faces < (1ll << 31), "bff_render_mesh_depth_u16: 2^31 triangles or more");
+    const int64_t total = (int64_t)n_frames * depth_h * depth_w;
+    BFF_LIMIT(ceil_div(ceil_div(total, 4), 256) < (1ll << 31), "bff_render_mesh_depth_u16: too many texels for one launch");
+    if (n_frames == 0) return BFF_OK;
+    BFF_REQUIRE(out_u16, "bff_render_mesh_depth_u16: null pointer");
+    hipStream_t st = as_stream(stream);
+    if (n_faces == 0 || n_vertices == 0) {                           // nothing is drawn: every texel is "no depth"
+        hipError_t e = hipMemsetAsync(out_u16, 0, sizeof(uint16_t) * (size_t)total, st);
+        if (e != hipSuccess) return fail((int)e, "bff_render_mesh_depth_u16: memset: %s", hipGetErrorString(e));
+        return BFF_OK;
+    }
+    BFF_REQUIRE(vertices && faces && inv_pose && cam_intr_host && scratch_u32, "bff_render_mesh_depth_u16: null pointer");
+    hipError_t e = hipMemsetAsync(scratch_u32, 0xff, sizeof(uint32_t) * (size_t)total, st);
+    if (e != hipSuccess) return fail((int)e, "bff_render_mesh_depth_u16: memset: %s", hipGetErrorString(e));
+    CameraK K;
+    for (int i = 0; i < 9; ++i) K.k[i] = cam_intr_host[i];
+    const int64_t gx = ceil_div(n_faces, kRmBlock);                  // < 2^23
+    int fpb = frames_per_block;
+    if (fpb == 0) {                                                  // >= ~4096 blocks in flight, tiles of up to 8 frames
+        fpb = (int)((int64_t)n_frames * gx / 4096);
+        fpb = fpb < 1 ? 1 : (fpb > 8 ? 8 : fpb);
+    }
+    dim3 grid((unsigned)gx, (unsigned)ceil_div(n_frames, fpb));
+    render_mesh_depth_kernel<<<grid, kRmBlock, 0, st>>>(vertices, n_vertices, nv_pad, faces, n_faces, inv_pose, K, n_frames,
+                                                        fpb, height, width, depth_h, depth_w, scratch_u32);
+    int rc = launched("bff_render_mesh_depth_u16");
+    if (rc != BFF_OK) return rc;
+    return narrow_frames(scratch_u32, total, out_u16, st, "bff_render_mesh_depth_u16");
 }

@@ -30,11 +30,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .scene import (DeviceScene, SceneGeometry, class_inv_poses, class_word_bits, concat_confidences, confidence_dtype,
-                    count_geometry_viewed, depth_from_cloud_stride, device_scene, frame_table, frame_union, label_ids,
-                    masks_all_rle, new_geometry, padded_points, prepare_class, prepare_geometry, prepare_scene,
-                    raw_depth_on_device, rendered_depth_on_device, run_tables, slots_on_first_use,
-                    viewed_frame_ids, with_viewed_counts)
+from .scene import (DeviceScene, SceneGeometry, checked_mesh, class_inv_poses, class_word_bits, concat_confidences,
+                    confidence_dtype, count_geometry_viewed, depth_from_mesh_stride, device_scene, frame_table, frame_union,
+                    label_ids, masks_all_rle, mesh_for_render, new_geometry, padded_points, prepare_class,
+                    prepare_geometry, prepare_scene, raw_depth_on_device, rendered_depth_on_device, rendered_depth_stride,
+                    run_tables, slots_on_first_use, viewed_frame_ids, with_viewed_counts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libbff_host.so")
@@ -194,13 +194,16 @@ def _geometry_to_device(scene, cfg, ids, n_viewed, dev, staging, n_threads, lap=
     inv = np.linalg.inv(np.stack([np.asarray(scene.poses[f], dtype=np.float64) for f in ids])).reshape(len(ids), 16) \
         if ids else np.zeros((0, 16))
     lap("pose inverses")
-    stride = depth_from_cloud_stride(cfg)
+    stride = rendered_depth_stride(cfg)
     if stride:                                       # no depth frames: rendered from the cloud, so the cloud goes first
+        mesh = checked_mesh(scene, pts.shape[0]) if depth_from_mesh_stride(cfg) else None    # raises before any upload
         xyz, unsort, perm, bounds = _cloud_to_device(pts, dev, staging)
         lap("cloud (copy to pinned, enqueue, layout)")
+        if mesh is not None:
+            mesh = _mesh_to_device(mesh, xyz, pts.shape[0], unsort, dev, staging)
         depth3 = _depth_to_device(scene, ids, pts.shape[0], h, w, dev, staging, n_threads,
-                                  cloud=(xyz, inv, scene.cam_intr, stride, bounds))
-        lap("depth (rendered from the cloud)")
+                                  cloud=(xyz, inv, scene.cam_intr, stride, bounds, mesh))
+        lap("depth (rendered from the cloud / the mesh)")
         return new_geometry(scene, h, w, pts.shape[0], ids, inv, n_viewed, xyz, depth3, bounds, unsort, perm)
     depth3 = _depth_to_device(scene, ids, pts.shape[0], h, w, dev, staging, n_threads)
     if depth3 is None:
@@ -256,17 +259,18 @@ def _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads, cloud=N
     """The frames `depth_ids` of a scene on the device, in that order (scene.host_depth_to_device's layout rules): packed
     into pinned staging by native threads and uploaded as ONE asynchronous copy.  -> (depth, depth_raw, depth_size), or
     None when the frames are of mixed sizes / dtypes (the caller takes the exact slow path).
-    cloud = (xyz, the frames' inverse poses on the host, K, stride, tile bounds): the scene has no depth frames (config key
-    depth_from_cloud); they are rendered from the cloud already laid out on the device, on the current stream
-    (scene.rendered_depth_on_device) -- no staging is taken and nothing crosses the bus but the poses."""
+    cloud = (xyz, the frames' inverse poses on the host, K, stride, tile bounds, mesh): the scene has no depth frames (config
+    key depth_from_cloud or depth_from_mesh); they are rendered from the cloud already laid out on the device, or from
+    the mesh on the device (_mesh_to_device; None: from the cloud), on the current stream
+    (scene.rendered_depth_on_device) -- no depth staging is taken and nothing crosses the bus but the poses."""
     if cloud is not None:
-        xyz, inv, cam_intr, stride, bounds = cloud
+        xyz, inv, cam_intr, stride, bounds, mesh = cloud
         inv_dev = None
         if inv.size:
             pstage = staging.get("render.poses", inv.nbytes)
             pstage.numpy()[:inv.nbytes].view(np.float64)[:] = inv.reshape(-1)
             inv_dev = pstage[:inv.nbytes].view(torch.float64).view(-1, 16).to(dev, non_blocking=True)
-        return rendered_depth_on_device(xyz, n, inv, cam_intr, h, w, stride, bounds, inv_pose_dev=inv_dev)
+        return rendered_depth_on_device(xyz, n, inv, cam_intr, h, w, stride, bounds, inv_pose_dev=inv_dev, mesh=mesh)
     raw_depth = getattr(scene, "depths_raw", None)
     src = raw_depth if raw_depth is not None else scene.depths
     frames = [src[f] for f in depth_ids]
@@ -299,6 +303,19 @@ def _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads, cloud=N
         return flat.view(torch.float32).view(len(frames), h * w).to(dev, non_blocking=True), None, None
     raw_dev = flat.view(torch.int16).view((len(frames),) + f0.shape).to(dev, non_blocking=True)
     return raw_depth_on_device(raw_dev, n, h, w)
+
+
+def _mesh_to_device(mesh, xyz, n, unsort, dev, staging):
+    """scene.checked_mesh's host triple -> scene.mesh_for_render's device triple: the faces (and the mesh's own vertices,
+    where it has them) travel through pinned staging like the other small tables, enqueued on the current stream."""
+    faces, verts, nv = mesh
+
+    def up(name, a, dtype):
+        stage = staging.get(name, a.nbytes)
+        np.copyto(stage.numpy()[:a.nbytes].view(a.dtype).reshape(a.shape), a)
+        return stage[:a.nbytes].view(dtype).view(a.shape).to(dev, non_blocking=True)
+    faces_dev = up("render.faces", faces, torch.int32) if faces.size else torch.zeros((0, 3), dtype=torch.int32, device=dev)
+    return mesh_for_render(faces_dev, xyz, n, unsort, None if verts is None else up("render.vertices", verts, torch.float64), nv)
 
 
 def _frames_inside(frames, held):

@@ -121,10 +121,41 @@ def decode_depth_pngs(paths, out: np.ndarray = None, n_threads: int = 4) -> np.n
     return frames
 
 
+def read_scene_mesh(cfg, scene_id: str, n_points: int):
+    """The triangle mesh of a scene (config key depth_from_mesh): scene_mesh_dir/<scene_id>.npz, read without pickle.
+    `faces` (T, 3) of any integer dtype; `vertices` (V, 3) float is optional -- without it the faces index the rows of
+    <scene_id>.npy (ScanNet: the cloud is the mesh's vertex array), with it the mesh is independent of the cloud
+    (ScanNet++).  -> (faces int32, vertices or None); a bad shape, dtype or index is a ValueError here, on the host."""
+    from .scene import checked_faces
+    mesh_dir = cfg.get("scene_mesh_dir")
+    if not mesh_dir:
+        raise ValueError("depth_from_mesh is set but scene_mesh_dir is not")
+    path = os.path.join(mesh_dir, f"{scene_id}.npz")
+    with np.load(path, allow_pickle=False) as z:
+        if "faces" not in z.files:
+            raise ValueError(f"{path}: no array `faces`")
+        faces = z["faces"]
+        vertices = z["vertices"] if "vertices" in z.files else None
+    if vertices is not None and (vertices.ndim != 2 or vertices.shape[1] != 3 or not np.issubdtype(vertices.dtype, np.floating)):
+        raise ValueError(f"{path}: vertices: a float array of shape (V, 3) expected, got {vertices.dtype} {vertices.shape}")
+    return checked_faces(faces, n_points if vertices is None else vertices.shape[0]), vertices
+
+
+def _scene_without_depth(cfg, scene_id, **fields) -> SceneInputs:
+    """The scene of a config that renders its depth (depth_from_cloud / depth_from_mesh): depth/ is neither listed nor
+    read; with depth_from_mesh the mesh file is."""
+    from .scene import depth_from_mesh_stride
+    faces = vertices = None
+    if depth_from_mesh_stride(cfg):
+        faces, vertices = read_scene_mesh(cfg, scene_id, fields["points"].shape[0])
+    return SceneInputs(scene_id=scene_id, depths={}, faces=faces, mesh_vertices=vertices, **fields)
+
+
 def load_scene(cfg, cls: str, scene_id: str, depth_on_device: bool = False, staging=None) -> SceneInputs:
     """Everything P:370-400 + the per-frame files of P:422-436 and P:526-563 for one scene.
-    With the config key depth_from_cloud on, no depth file is read (`depths` stays empty, `depths_raw` None): the scene
-    directory needs no depth/ folder and the preparation renders the frames from the cloud.
+    With the config key depth_from_cloud or depth_from_mesh on, no depth file is read (`depths` stays empty, `depths_raw`
+    None): the scene directory needs no depth/ folder and the preparation renders the frames from the cloud or from the
+    mesh (read_scene_mesh).
     depth_on_device: keep the depth frames as raw uint16 (`SceneInputs.depths_raw`), decoded as one batch by the native
     PNG decoder; prepare_scene uploads them as they are and the sweep does /1000 + resize per point.  staging (an
     ingest.Staging, given by the loader thread that will upload the scene): the frames are decoded straight into its
@@ -139,16 +170,16 @@ def load_scene(cfg, cls: str, scene_id: str, depth_on_device: bool = False, stag
     mask_2d = torch.load(os.path.join(cfg.mask_2d_dir, cls, f"{scene_id}.pth"), weights_only=False)
     color_dir = os.path.join(scene_dir, "color")
     color_files = [f for f in os.listdir(color_dir) if f.endswith(".jpg")] if os.path.isdir(color_dir) else []
-    from .scene import depth_from_cloud_stride, viewed_frame_ids, with_viewed_counts
+    from .scene import rendered_depth_stride, viewed_frame_ids, with_viewed_counts
     # frames in upload order: mask frames in list order, then the frames only the detection-ratio sweep looks at
     need = list(dict.fromkeys(fr["frame_id"][:-4] for fr in mask_2d))
     if with_viewed_counts(cfg):
         need = list(dict.fromkeys(need + viewed_frame_ids(color_files, cfg.downsample_ratio)))
     w, h = int(cfg.width_2d), int(cfg.height_2d)
     poses = {f: read_matrix_txt(os.path.join(scene_dir, "pose", f"{f}.txt")) for f in need}      # P:422
-    if depth_from_cloud_stride(cfg):                 # depth is rendered from the cloud: depth/ is neither listed nor read
-        return SceneInputs(scene_id=scene_id, points=points, cam_intr=cam_intr, poses=poses, depths={},
-                           mask_2d=mask_2d, color_files=color_files, height=h, width=w)
+    if rendered_depth_stride(cfg):                   # depth is rendered on the device: depth/ is neither listed nor read
+        return _scene_without_depth(cfg, scene_id, points=points, cam_intr=cam_intr, poses=poses, mask_2d=mask_2d,
+                                    color_files=color_files, height=h, width=w)
     if depth_on_device:
         paths = [os.path.join(scene_dir, "depth", f"{f}.png") for f in need]
         out = None
@@ -176,7 +207,7 @@ def load_scene_classes(cfg, classes, scene_id: str, depth_on_device: bool = Fals
     """load_scene for several query classes of one scene: the cloud, the poses and the depth frames are read ONCE --
     every frame any class's mask list names, then the detection-ratio sweep's frames -- plus each class's
     mask_2d/<cls>/<scene>.pth.  -> scene.SceneClasses (its `scene` holds an empty mask_2d)."""
-    from .scene import SceneClasses, depth_from_cloud_stride, frame_union, viewed_frame_ids, with_viewed_counts
+    from .scene import SceneClasses, frame_union, rendered_depth_stride, viewed_frame_ids, with_viewed_counts
     scene_dir = os.path.join(cfg.scene_2d_dir, scene_id)
     cam_intr = read_matrix_txt(os.path.join(scene_dir, "intrinsic", "intrinsic_color.txt"))     # P:376
     points = np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"))                         # P:387
@@ -188,9 +219,9 @@ def load_scene_classes(cfg, classes, scene_id: str, depth_on_device: bool = Fals
     need = frame_union([masks[c] for c in classes], viewed)          # the geometry's slot order (upload order)
     w, h = int(cfg.width_2d), int(cfg.height_2d)
     poses = {f: read_matrix_txt(os.path.join(scene_dir, "pose", f"{f}.txt")) for f in need}      # P:422
-    if depth_from_cloud_stride(cfg):                 # depth is rendered from the cloud: depth/ is neither listed nor read
-        scene = SceneInputs(scene_id=scene_id, points=points, cam_intr=cam_intr, poses=poses, depths={},
-                            mask_2d=[], color_files=color_files, height=h, width=w)
+    if rendered_depth_stride(cfg):                   # depth is rendered on the device: depth/ is neither listed nor read
+        scene = _scene_without_depth(cfg, scene_id, points=points, cam_intr=cam_intr, poses=poses, mask_2d=[],
+                                     color_files=color_files, height=h, width=w)
     elif depth_on_device:
         paths = [os.path.join(scene_dir, "depth", f"{f}.png") for f in need]
         out = None

@@ -368,38 +368,110 @@ def host_depth_to_device(scene, ids, n_points, h, w, dev, raw_depth_resident=Non
     return (out, None, None) if raw is None else raw_depth_on_device(out, n_points, h, w, raw_depth_resident)
 
 
-def depth_from_cloud_stride(cfg) -> int:
-    """The optional config key `depth_from_cloud`: 0 (or absent) = the scene brings its depth frames; an integer stride
-    s >= 1 = they are rendered from the cloud at (ceil(height_2d / s), ceil(width_2d / s))."""
-    v = cfg.get("depth_from_cloud", 0)
+def _stride_key(cfg, key) -> int:
+    v = cfg.get(key, 0)
     if v is None or v is False:
         return 0
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
-        raise ValueError(f"depth_from_cloud: a non-negative integer stride expected, got {v!r}")
+        raise ValueError(f"{key}: a non-negative integer stride expected, got {v!r}")
     return int(v)
+
+
+def depth_from_cloud_stride(cfg) -> int:
+    """The optional config key `depth_from_cloud`: 0 (or absent) = the scene brings its depth frames; an integer stride
+    s >= 1 = they are rendered from the cloud at (ceil(height_2d / s), ceil(width_2d / s))."""
+    return _stride_key(cfg, "depth_from_cloud")
+
+
+def depth_from_mesh_stride(cfg) -> int:
+    """The optional config key `depth_from_mesh`: as depth_from_cloud, the frames rasterised from the scene's triangle
+    mesh (SceneInputs.faces / mesh_vertices; on disk scene_mesh_dir/<scene_id>.npz)."""
+    return _stride_key(cfg, "depth_from_mesh")
+
+
+def rendered_depth_stride(cfg) -> int:
+    """The stride of whichever of depth_from_cloud / depth_from_mesh is on (0 = neither: the scene brings its depth
+    frames); both at once is an error."""
+    cloud, mesh = depth_from_cloud_stride(cfg), depth_from_mesh_stride(cfg)
+    if cloud and mesh:
+        raise ValueError("depth_from_cloud and depth_from_mesh are both set: a scene's depth is rendered from one of them")
+    return cloud or mesh
 
 
 def rendered_depth_size(h, w, stride):
     return -(-h // stride), -(-w // stride)
 
 
+def checked_faces(faces, n_vertices) -> np.ndarray:
+    """The triangles of a mesh as contiguous int32 (T, 3), checked on the host before anything is uploaded: an integer
+    array of that shape whose indices lie in [0, n_vertices).  The kernel never sees a bad index."""
+    if faces is None:
+        raise ValueError("depth_from_mesh: the scene has no faces")
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"mesh faces: shape (T, 3) expected, got {f.shape}")
+    if f.dtype == np.bool_ or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"mesh faces: an integer array expected, got {f.dtype}")
+    if f.shape[0] >= 1 << 31:
+        raise ValueError(f"mesh faces: {f.shape[0]} triangles, at most 2^31 - 1")
+    if f.size and (int(f.min()) < 0 or int(f.max()) >= n_vertices):
+        raise ValueError(f"mesh faces: indices {int(f.min())} .. {int(f.max())} outside [0, {n_vertices})")
+    return np.ascontiguousarray(f, dtype=np.int32)
+
+
+def checked_mesh(scene, n_points):
+    """-> (faces int32 (T, 3), the mesh's own vertices as f64 SoA [3][nv_pad] or None, number of vertices).  Without
+    `mesh_vertices` the faces index the rows of the cloud (ScanNet: the cloud is the mesh's vertex array); with them the
+    mesh is independent of the cloud (ScanNet++)."""
+    verts = getattr(scene, "mesh_vertices", None)
+    if verts is None:
+        return checked_faces(getattr(scene, "faces", None), n_points), None, n_points
+    v = np.asarray(verts)
+    if v.ndim != 2 or v.shape[1] != 3 or not np.issubdtype(v.dtype, np.floating):
+        raise ValueError(f"mesh vertices: a float array of shape (V, 3) expected, got {v.dtype} {v.shape}")
+    faces = checked_faces(getattr(scene, "faces", None), v.shape[0])
+    soa = np.zeros((3, padded_points(v.shape[0])), dtype=np.float64)
+    soa[:, :v.shape[0]] = v.T
+    return faces, soa, v.shape[0]
+
+
+def mesh_for_render(faces, xyz, n_points, unsort=None, vertices=None, n_vertices=0):
+    """A checked mesh on the device as bff_render_mesh_depth_u16 takes it -> (vertices f64 [3][nv_pad], their number,
+    faces int32 [T][3]).  faces: int32 [T][3] on xyz's device.  Without `vertices` (the mesh's own, SoA on the device) the
+    faces index the cloud: they are remapped into the sorted point order through `unsort` (None: the cloud was left as
+    it is), and the sorted cloud `xyz` is the vertex array -- no second copy of it.  The triangles are launched sorted by
+    their smallest vertex position, so that the vertices a wave gathers are neighbours: the one device sort per scene."""
+    if vertices is None:
+        vertices, n_vertices = xyz, n_points
+        if unsort is not None and faces.numel():
+            faces = unsort[faces.long()]
+    if faces.shape[0] > 1:
+        faces = faces[torch.sort(faces.min(dim=1).values).indices]
+    return vertices, int(n_vertices), faces.to(torch.int32).contiguous()
+
+
 def rendered_depth_on_device(xyz, n_points, inv_pose_host, cam_intr, h, w, stride, tile_bounds=None,
-                             raw_depth_resident=None, inv_pose_dev=None):
+                             raw_depth_resident=None, inv_pose_dev=None, mesh=None):
     """host_depth_to_device for a scene without depth frames: one frame per row of inv_pose_host (the slots' inverse
     poses, f64 [slots][16]) rendered from the sorted cloud `xyz` on its device (bff_render_depth_u16, one call for all
     slots, on the current stream) at 1 / stride of the working resolution, handed to raw_depth_on_device like the PNGs'
     uint16 frames -> (depth, depth_raw, depth_size).  inv_pose_dev: the same poses already on the device (ingest.py
-    sends them through its pinned staging)."""
+    sends them through its pinned staging).  mesh (mesh_for_render's triple): the frames are rasterised from these
+    triangles instead (bff_render_mesh_depth_u16)."""
     from . import _lib
     dev = xyz.device
     if dev.type != "cuda":
-        raise ValueError("depth_from_cloud needs a GPU device (there is no CPU renderer)")
+        raise ValueError("depth_from_cloud / depth_from_mesh need a GPU device (there is no CPU renderer)")
     if not len(inv_pose_host):
         return torch.zeros((0, h * w), dtype=torch.float32, device=dev), None, None
     dh, dw = rendered_depth_size(h, w, stride)
     inv = inv_pose_dev if inv_pose_dev is not None else \
         torch.as_tensor(np.ascontiguousarray(inv_pose_host, dtype=np.float64).reshape(-1, 16)).to(dev)
-    raw = _lib.render_depth(xyz, n_points, inv, np.asarray(cam_intr, dtype=np.float64)[:3, :3], h, w, dh, dw, tile_bounds)
+    k33 = np.asarray(cam_intr, dtype=np.float64)[:3, :3]
+    if mesh is not None:
+        raw = _lib.render_mesh_depth(mesh[0], mesh[1], mesh[2], inv, k33, h, w, dh, dw)
+    else:
+        raw = _lib.render_depth(xyz, n_points, inv, k33, h, w, dh, dw, tile_bounds)
     return raw_depth_on_device(raw, n_points, h, w, raw_depth_resident)
 
 
@@ -471,7 +543,8 @@ def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -
     soa, perm, unsort, n, _ = cloud_host_layout(scene.points, sort_points)
     inv = np.stack([np.linalg.inv(np.asarray(scene.poses[f], dtype=np.float64)).reshape(16) for f in ids]) if ids \
         else np.zeros((0, 16))                                                      # :425
-    stride = depth_from_cloud_stride(cfg)
+    stride = rendered_depth_stride(cfg)
+    mesh = checked_mesh(scene, n) if depth_from_mesh_stride(cfg) else None        # raises before anything is uploaded
     if not stride:
         depth3 = host_depth_to_device(scene, ids, n, h, w, dev, raw_depth_resident)
     xyz = torch.as_tensor(soa).to(dev)
@@ -479,10 +552,15 @@ def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -
     if dev.type == "cuda" and n:
         from . import _lib
         bounds = _lib.point_tile_bounds(xyz, n)          # built once per scene, next to the spatial sort it relies on
-    if stride:                                           # no depth frames: the cloud itself says what each camera sees
-        depth3 = rendered_depth_on_device(xyz, n, inv, scene.cam_intr, h, w, stride, bounds, raw_depth_resident)
     t32 = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-    return new_geometry(scene, h, w, n, ids, inv, n_viewed, xyz, depth3, bounds, t32(unsort), t32(perm))
+    unsort = t32(unsort)
+    if stride:                                           # no depth frames: the cloud or the mesh says what each camera sees
+        if mesh is not None and dev.type == "cuda":
+            faces, verts, nv = mesh
+            mesh = mesh_for_render(torch.as_tensor(faces).to(dev), xyz, n, unsort,
+                                   None if verts is None else torch.as_tensor(verts).to(dev), nv)
+        depth3 = rendered_depth_on_device(xyz, n, inv, scene.cam_intr, h, w, stride, bounds, raw_depth_resident, mesh=mesh)
+    return new_geometry(scene, h, w, n, ids, inv, n_viewed, xyz, depth3, bounds, unsort, t32(perm))
 
 
 def masks_all_rle(ft: FrameTable) -> bool:

@@ -49,6 +49,9 @@ class SceneInputs:
                                                           # when given, /1000 + resize run on the device
     depth_staged: Optional[tuple] = None                 # (ingest.Staging, frame ids): depths_raw already lies in that
                                                           # staging's pinned "depth" buffer in this order (io.load_scene)
+    faces: Optional[np.ndarray] = None                   # (T, 3) integers: the scene's triangle mesh (config key
+                                                          # depth_from_mesh); they index the rows of `points` ...
+    mesh_vertices: Optional[np.ndarray] = None           # ... unless the mesh brings its own (V, 3) float vertices
 
 
 def _hash32(x: torch.Tensor) -> torch.Tensor:
@@ -256,6 +259,49 @@ def make_scene(shape="c1", seed: int = 0, device="cpu", query: str = "table", n_
     return SceneInputs(scene_id=f"scene{seed:04d}_00", points=points, cam_intr=cam_intr, poses=poses,
                        depths=depths, mask_2d=mask_2d, color_files=color_files, stage1=stage1,
                        height=h, width=w, point_object=obj)
+
+
+def _box_mesh(lo, hi, skip_bottom, cell):
+    """The faces of an axis-aligned box as grids of cells at most `cell` wide, two triangles per cell
+    -> (vertices (V, 3), faces (T, 3) int64).  The faces of the box share no vertices."""
+    verts, tris, base = [], [], 0
+    d = hi - lo
+    for ax in range(3):
+        a1, a2 = (ax + 1) % 3, (ax + 2) % 3
+        n1, n2 = max(1, int(math.ceil(d[a1] / cell))), max(1, int(math.ceil(d[a2] / cell)))
+        g1, g2 = np.meshgrid(np.linspace(lo[a1], hi[a1], n1 + 1), np.linspace(lo[a2], hi[a2], n2 + 1), indexing="ij")
+        i, j = np.meshgrid(np.arange(n1), np.arange(n2), indexing="ij")
+        c = (i * (n2 + 1) + j).reshape(-1)
+        cells = np.concatenate([np.stack([c, c + n2 + 1, c + n2 + 2], 1), np.stack([c, c + n2 + 2, c + 1], 1)])
+        for side in (0, 1):
+            if skip_bottom and ax == 2 and side == 0:
+                continue
+            v = np.empty(g1.shape + (3,))
+            v[..., a1], v[..., a2], v[..., ax] = g1, g2, hi[ax] if side else lo[ax]
+            verts.append(v.reshape(-1, 3))
+            tris.append(cells + base)
+            base += v.shape[0] * v.shape[1]
+    return np.concatenate(verts), np.concatenate(tris)
+
+
+def make_scene_mesh(seed: int = 0, n_objects: int = 10, n_vertices: int = None):
+    """The surfaces make_scene(seed=seed, n_objects=n_objects) samples its cloud from -- the room and the cuboids -- as a
+    triangle mesh -> (vertices (V, 3) float64, faces (T, 3) int64).  n_vertices: tessellated to about that many vertices
+    (None: one cell per face)."""
+    lo, hi = _cuboids(np.random.default_rng(seed), n_objects)          # make_scene's first draws
+    boxes = [(np.zeros(3), np.asarray(ROOM, dtype=np.float64), False)] + [(lo[k], hi[k], True) for k in range(lo.shape[0])]
+    cell = float("inf")
+    if n_vertices:
+        area = sum(2 * (d[0] * d[2] + d[1] * d[2]) + (1 if skip else 2) * d[0] * d[1]
+                   for d, skip in ((b[1] - b[0], b[2]) for b in boxes))
+        cell = math.sqrt(area / n_vertices)
+    verts, tris, base = [], [], 0
+    for blo, bhi, skip in boxes:
+        v, t = _box_mesh(blo, bhi, skip, cell)
+        verts.append(v)
+        tris.append(t + base)
+        base += v.shape[0]
+    return np.concatenate(verts), np.concatenate(tris)
 
 
 def with_sensor_depth(scene: SceneInputs, factor: int = 2) -> SceneInputs:

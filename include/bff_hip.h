@@ -32,7 +32,7 @@ extern "C" {
 #define BFF_E_ARG (-1)      /* null pointer / negative size / unsupported parameter */
 #define BFF_E_LIMIT (-2)    /* size beyond what a kernel supports (documented per call) */
 
-#define BFF_ABI_VERSION 10
+#define BFF_ABI_VERSION 11
 
 int bff_abi_version(void);
 const char *bff_last_error(void);
@@ -220,6 +220,48 @@ int bff_render_depth_u16(const double *xyz, int64_t n_points, int64_t n_pad, con
                          const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width,
                          int32_t depth_h, int32_t depth_w, int32_t frames_per_block, uint32_t *scratch_u32,
                          uint16_t *out_u16, const double *tile_bounds, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Depth frames rendered from a triangle mesh: what bff_render_depth_u16 supplies, without its holes (fine frames) and
+ * without the nearest point of a texel shadowing the whole texel (coarse frames).  out_u16, scratch_u32, inv_pose,
+ * cam_intr_host (K, row-major) and frames_per_block are bff_render_depth_u16's; the call fills the scratch itself,
+ * allocates nothing and synchronises nothing.
+ *   vertices  float64 SoA [3][nv_pad], n_vertices of them
+ *   faces     int32 [n_faces][3] on the device, indices into the vertices.  The caller has validated them
+ *             (0 <= index < n_vertices); a triangle that names another index is not drawn.  The frames do not depend
+ *             on the triangles' order.
+ * Every operation below is an IEEE float64 operation in the order written, without contraction.
+ * Vertex n in frame f:  c_0, c_1, c_2 by the fma chains of bff_project_views (k ascending from +0.0), so the vertex's
+ *   depth c_2 is exactly what the visibility test compares.  Screen position in pixels, pixel centres at integers:
+ *     px = ((K00 * c_0 + K01 * c_1) + K02 * c_2) / c_2,  py = ((K10 * c_0 + K11 * c_1) + K12 * c_2) / c_2
+ *   (plain products and sums, no fma), and r = 1.0 / c_2.
+ * Triangle in frame f:  takes part iff all three vertices have c_2 > 0, |px| < 2^24 and |py| < 2^24 (comparisons on the
+ *   doubles: NaN fails).  A triangle that crosses the camera plane is therefore dropped, not clipped.
+ * Sample point of texel (i, j):  X = (j + 0.5) * (width / depth_w) - 0.5,  Y = (i + 0.5) * (height / depth_h) - 0.5
+ *   (the quotients in float64): the pixel position the bilinear resize maps to the centre of that texel.
+ * Coverage, with (x_k, y_k) = (px, py) of the triangle's vertex k:
+ *     e0 = (x1 - X) * (y2 - Y) - (x2 - X) * (y1 - Y)
+ *     e1 = (x2 - X) * (y0 - Y) - (x0 - X) * (y2 - Y)
+ *     e2 = (x0 - X) * (y1 - Y) - (x1 - X) * (y0 - Y)
+ *     S  = (e0 + e1) + e2
+ *   the texel is covered iff S != 0 and (e0, e1, e2 all >= 0, or all <= 0): both windings count, and there is no fill
+ *   rule -- a texel on a shared edge may be covered twice, which a minimum does not notice.
+ * Depth:  z = S / ((e0 * r0 + e1 * r1) + e2 * r2) (perspective-correct), m = rint(z * 1000.0); the texel takes m iff
+ *   1 <= m <= 65535.
+ * Result:  out[f][i][j] = the minimum m over all triangles, 0 if there is none.  A minimum of integers has no order:
+ *   the frames are the same bytes on every run.  The result is defined over all texels; the texel box a triangle's
+ *   thread walks is an optimisation.
+ * Limits: those of bff_render_depth_u16, and n_faces < 2^31.  n_frames = 0 returns at once; n_faces = 0 (or no vertex) gives frames
+ * of zeros. */
+int bff_render_mesh_depth_u16(const double *vertices, int64_t n_vertices, int64_t nv_pad, const int32_t *faces,
+                              int64_t n_faces, const double *inv_pose, const double *cam_intr_host, int32_t n_frames,
+                              int32_t height, int32_t width, int32_t depth_h, int32_t depth_w, int32_t frames_per_block,
+                              uint32_t *scratch_u32, uint16_t *out_u16, void *stream);
+
+/* Texels of a triangle's clipped texel box up to which the triangle's own lane walks the box; a larger box is walked
+ * by the whole wave.  The box of a triangle along one axis: the texels t with floor((lo + 0.5) / s - 0.5) - 1 <= t <=
+ * ceil((hi + 0.5) / s - 0.5) + 1, clipped to the frame (lo, hi: the vertices' extent in pixels, s: pixels per texel). */
+int bff_mesh_lane_box(void);
 
 /* Frustum culling for bff_project_views (optional, exact).  bounds: float64 [ceil(n_points / bff_point_tile_size())][6]
  * = (xmin, ymin, zmin, xmax, ymax, zmax) of every tile of bff_point_tile_size() consecutive points -- the points
