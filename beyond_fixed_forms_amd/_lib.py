@@ -23,6 +23,8 @@ _P, _I, _L, _D, _F = c_void_p, c_int32, c_int64, c_double, c_float
 SIGNATURES = {
     "bff_rle_to_maskbits": [_P, _P, _P, _P, _I, _L, _I, _P, _P, _P],
     "bff_rle_to_labels": [_P, _P, _P, _P, _I, _L, _I, _P, _P, _P, _P],
+    "bff_mask_row_directory": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "bff_project_views_lookup": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P],
     "bff_masks2d_count": [_P, _I, _L, _P, _P, _P],
     "bff_masks2d_runs": [_P, _I, _L, _P, _P, _P, _P],
     "bff_project_views": [_P, _L, _L, _P, _P, _I, _P, _P, _I, _I, _D, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P],
@@ -78,7 +80,7 @@ SIGNATURES = {
     "bff_depth_from_u16": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P],
 }
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
-         "bff_masks2d_tile_pixels": (c_int32, []),
+         "bff_masks2d_tile_pixels": (c_int32, []), "bff_mask_lookup_rows": (c_int32, [c_int32, c_int32, c_int64]),
          "bff_chunk_mask_words": (c_int32, [c_int64]), "bff_label_plane_stride": (c_int64, [c_int64]), "bff_resolve_overlaps_max_rows": (c_int32, []),
          "bff_point_tile_size": (c_int32, []), "bff_mesh_lane_box": (c_int32, []), "bff_depth_tiled_texels": (c_int64, [c_int32, c_int32]), "bff_merge_scratch_words": (c_int64, [c_int32]), "bff_merge_uses_chunk_bound": (c_int32, [c_int64]),
          "bff_profile_next_merge": (c_int32, [_P, _P]), "bff_group_slice_cap": (c_int32, [c_int32, c_int32]),
@@ -87,7 +89,7 @@ PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, [
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class BffLibraryError(RuntimeError):
@@ -298,6 +300,46 @@ def project_views(xyz_soa, n_points, inv_pose, cam_intr, depth, depth_index, hei
          _ptr(frame_nmask, i32), _ptr(frame_flags, i32), _ptr(rows, i64),
          0 if rows is None else rows.shape[0], nw, _ptr(chunk_mask, i64), _ptr(masked_count, i32),
          _ptr(viewed_count, i32), _ptr(tile_bounds, f64))
+
+
+def mask_row_directory(run_start, run_end, mask_run_offs, n_masks, height, width, mask_tab=None, mask_dir=None):
+    """Boxes and per-row entries of n_masks 2-D masks out of their run tables (bff_mask_row_directory).  Returns
+    (mask_tab int32 [n_masks + 1][4], mask_dir int32 [n_masks * height]); the words are unsigned (csrc/mask_rows.h), the
+    directory is filled up to mask_tab[n_masks][2] entries."""
+    dev = mask_run_offs.device
+    if mask_tab is None:
+        mask_tab = torch.empty((n_masks + 1, 4), dtype=i32, device=dev)
+    if mask_dir is None:
+        mask_dir = torch.empty(max(n_masks * height, 1), dtype=i32, device=dev)
+    call("bff_mask_row_directory", _ptr(run_start, i32), _ptr(run_end, i32), _ptr(mask_run_offs, i32), n_masks, height,
+         width, _ptr(mask_tab, i32), _ptr(mask_dir, i32))
+    return mask_tab, mask_dir
+
+
+def mask_lookup_rows(height, width, n_masks):
+    """Does the scene call look masks up in the row directory (True) or decode them (False)?  (BFF_MASK_LOOKUP)"""
+    return bool(load().bff_mask_lookup_rows(height, width, n_masks))
+
+
+def project_views_lookup(xyz_soa, n_points, inv_pose, cam_intr, depth, depth_index, height, width, depth_thresh,
+                         mask_tab, mask_dir, run_start, run_end, view_mask_offs, word_bits, frame_mask, frame_rowbase,
+                         frame_nmask, frame_flags, rows, masked_count, viewed_count, chunk_mask=None, tile_bounds=None,
+                         depth_size=None):
+    """project_views with the masks looked up in their row directory (mask_row_directory) instead of decoded planes."""
+    k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
+    if depth.dtype == torch.int16 or depth_size is not None:
+        hs, ws = (depth_size if depth_size is not None else depth.shape[1:3])
+        layout = 0 if depth_size is None else (2 if depth.dtype == f32 else 1)
+    else:
+        hs, ws, layout = 0, 0, -1
+        if depth.dtype != f32:
+            raise TypeError(f"expected float32 depth images, got {depth.dtype}")
+    call("bff_project_views_lookup", _ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(inv_pose, f64),
+         ctypes.cast(k, c_void_p), inv_pose.shape[0], _ptr(depth), int(hs), int(ws), layout, _ptr(depth_index, i32), height,
+         width, float(depth_thresh), _ptr(mask_tab, i32), _ptr(mask_dir, i32), _ptr(run_start, i32), _ptr(run_end, i32),
+         _ptr(view_mask_offs, i32), word_bits, _ptr(frame_mask, i32), _ptr(frame_rowbase, i32), _ptr(frame_nmask, i32),
+         _ptr(frame_flags, i32), _ptr(rows, i64), 0 if rows is None else rows.shape[0], (n_points + 63) // 64,
+         _ptr(chunk_mask, i64), _ptr(masked_count, i32), _ptr(viewed_count, i32), _ptr(tile_bounds, f64))
 
 
 def count_viewed(xyz_soa, n_points, inv_pose, cam_intr, depth, depth_index, height, width, depth_thresh, viewed_count,

@@ -15,6 +15,7 @@
 #include <hip/hip_ext.h>
 
 #include "common.h"
+#include "mask_rows.h"
 
 namespace bff {
 
@@ -105,7 +106,41 @@ __device__ __forceinline__ float sensor_texel(const void *frame, uint32_t t, con
 
 __device__ __forceinline__ void lds_phase_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-template <typename WordT, bool kLabels, bool kRaw>
+// two uint16 per register (a pixel as column | row << 16): component-wise minimum / maximum
+__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// component-wise minimum (kMin) or maximum of v over the 64 lanes, in every lane: six DPP steps as wave_xor_scan below
+// (lanes a step does not reach take the operation's identity), the total out of lane 63
+template <bool kMin>
+__device__ __forceinline__ uint32_t wave_reduce_pk_u16(uint32_t v)
+{
+    constexpr int id = kMin ? -1 : 0;
+#define BFF_DPP_PK(ctrl, rows) do { const uint32_t t_ = (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, ctrl, rows, 0xF, false); \
+                                    v = kMin ? pk_min_u16(v, t_) : pk_max_u16(v, t_); } while (0)
+    BFF_DPP_PK(0x111, 0xF);     // row_shr:1
+    BFF_DPP_PK(0x112, 0xF);     // row_shr:2
+    BFF_DPP_PK(0x114, 0xF);     // row_shr:4
+    BFF_DPP_PK(0x118, 0xF);     // row_shr:8
+    BFF_DPP_PK(0x142, 0xA);     // row_bcast:15 -> rows 1 and 3
+    BFF_DPP_PK(0x143, 0xC);     // row_bcast:31 -> rows 2 and 3
+#undef BFF_DPP_PK
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// kRows: the frame's masks are not decoded into `maskbits`; a visible point asks the masks' row directory (mask_rows.h)
+// at its pixel instead.  The block's <= kRowsFrames frames keep their mask tables in LDS behind the tap table.
+template <typename WordT, bool kLabels, bool kRaw, bool kRows = false>
 __global__ __launch_bounds__(kBlock) void project_views_kernel(
     const double *__restrict__ xyz, int64_t n_points, int64_t n_pad,
     const double *__restrict__ inv_pose, Intrinsics K, int n_frames, int frames_per_block,
@@ -117,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
     const int32_t *__restrict__ frame_flags,
     uint64_t *__restrict__ rows, int64_t nw, uint64_t *__restrict__ chunk_mask, int mw,
     int32_t *__restrict__ masked_count, int32_t *__restrict__ viewed_count,
-    const double *__restrict__ tile_bounds)
+    const double *__restrict__ tile_bounds, MaskRows mr)
 {
     // per wave: [bit][kPPT words] transposition buffer for the wave's sector of the frame's rows
     __shared__ uint64_t stage_all[kBlock / kWave][sizeof(WordT) * 8][kPPT];
@@ -143,6 +178,21 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
                 if (i < n_vec) dst[i] = v[q];
             }
         }
+        __syncthreads();
+    }
+    const uint4 *s_mtab = nullptr;
+    if constexpr (kRows) {
+        // mask tables of the block's frames: entry m of frame slot k at [k * kRowsMaskSlots + m], m <= the frame's masks
+        uint4 *dst = reinterpret_cast<uint4 *>(s_taps + (kRaw ? (3 * raw.n_taps + 3) / 4 * 4 : 0));
+        for (int i = (int)threadIdx.x; i < kRowsFrames * kRowsMaskSlots; i += kBlock) {
+            const int fk = i / kRowsMaskSlots, m = i - fk * kRowsMaskSlots;
+            const int f = (int)blockIdx.y * frames_per_block + fk;
+            if (fk < frames_per_block && f < n_frames) {
+                const int mi = frame_mask[f];
+                if (mi >= 0 && m <= frame_nmask[f]) dst[i] = mr.tab[mr.view_mask_offs[mi] + m];
+            }
+        }
+        s_mtab = dst;
         __syncthreads();
     }
 
@@ -221,9 +271,9 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
         const float *dimg = kRaw ? nullptr : reinterpret_cast<const float *>(depth) + (int64_t)depth_index[f] * hw;
         const char *rimg = kRaw ? reinterpret_cast<const char *>(depth) +
                                   (int64_t)depth_index[f] * raw.frame_stride * (raw.texel_f32 ? 4 : 2) : nullptr;
-        const int mi = maskbits ? frame_mask[f] : -1;
+        const int mi = (kRows || maskbits) ? frame_mask[f] : -1;
         const bool has_masks = mi >= 0;
-        const WordT *mimg = has_masks ? maskbits + (int64_t)mi * hw : nullptr;
+        const WordT *mimg = (!kRows && has_masks) ? maskbits + (int64_t)mi * hw : nullptr;
         const uint8_t *limg = (kLabels && has_masks) ? labels + (int64_t)mi * label_stride : nullptr;   // wave-uniform
         const uint32_t *smap = (segmap && has_masks) ? segmap + (int64_t)mi * seg_words * (kLabels ? 2 : 1) : nullptr;
         const int nm = has_masks ? frame_nmask[f] : 0;
@@ -331,6 +381,62 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
                         wv[j] = (WordT)(idx == 0 ? first4[j].x : idx == 1 ? first4[j].y : idx == 2 ? first4[j].z : first4[j].w);
                     } else {
                         wv[j] = *reinterpret_cast<const WordT *>(limg + (pix[j] & ~127) + 64 + sizeof(WordT) * idx);
+                    }
+                }
+            }
+        } else if constexpr (kRows) {
+            uint32_t bmin = 0xffffffffu, bmax = 0;         // bounding box of the wave's visible pixels
+#pragma unroll
+            for (int j = 0; j < kPPT; ++j) {
+                vis[j] = (pix[j] >= 0) && (dval[j] != 0.0f) && (fabs(cz[j] - (double)dval[j]) < thresh);
+                wv[j] = 0;
+                if (vis[j]) {
+                    bmin = pk_min_u16(bmin, (uint32_t)pu[j]);
+                    bmax = pk_max_u16(bmax, (uint32_t)pu[j]);
+                }
+            }
+            if (has_masks && __ballot(bmax >= bmin)) {     // wave-uniform; some lane has a visible point
+                const uint4 *ft = s_mtab + (f - f0) * kRowsMaskSlots;
+                bmin = wave_reduce_pk_u16<true>(bmin);
+                bmax = wave_reduce_pk_u16<false>(bmax);
+                // lane m: can mask m's box hold one of the wave's visible pixels at all?
+                bool may = false;
+                if (lane < nm) {
+                    const uint2 box = *reinterpret_cast<const uint2 *>(ft + lane);
+                    may = pk_min_u16(box.x, bmax) == box.x && pk_max_u16(box.y, bmin) == box.y;
+                }
+                uint64_t cand = __ballot(may);
+                // The candidates three at a time: a lane's directory entries of a round (<= 3 masks x 4 points) are all in
+                // flight before the first is looked at.  Masks and tables are wave-uniform: LDS broadcast reads.
+                constexpr int kRound = 3;                   // 128 VGPRs: four waves per SIMD, as the dense sweep (4: 132, three waves)
+                while (cand) {
+                    int mk[kRound];
+                    uint32_t ent[kRound][kPPT];
+#pragma unroll
+                    for (int k = 0; k < kRound; ++k) {
+                        mk[k] = cand ? __ffsll((unsigned long long)cand) - 1 : -1;
+                        cand &= cand - 1;                  // 0 stays 0
+                        if (mk[k] < 0) continue;
+                        const uint4 t = ft[mk[k]];
+#pragma unroll
+                        for (int j = 0; j < kPPT; ++j) {
+                            ent[k][j] = 0;
+                            const uint32_t p = (uint32_t)pu[j];
+                            if (vis[j] && pk_min_u16(pk_max_u16(p, t.x), t.y) == p)
+                                ent[k][j] = mr.dir[t.z + ((p >> 16) - (t.x >> 16))];
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < kRound; ++k) {
+                        if (mk[k] < 0) continue;
+#pragma unroll
+                        for (int j = 0; j < kPPT; ++j) {
+                            const uint32_t e = ent[k][j], u = (uint32_t)pu[j] & 0xffffu;
+                            bool in = (e & 0x7fffu) <= u && u < ((e >> 15) & 0x7fffu);
+                            if (e & kRowFlag)              // several runs on the row: the run table decides
+                                in = runs_cover(mr.run_start, mr.run_end, e, ft[mk[k]].w, ft[mk[k] + 1].w, pix[j]);
+                            if (in) wv[j] |= (WordT)1 << mk[k];
+                        }
                     }
                 }
             }
@@ -1097,7 +1203,7 @@ static int project_views_launch(const double *xyz, int64_t n_points, int64_t n_p
                                 const int32_t *frame_flags,
                                 uint64_t *rows, int64_t n_rows, int64_t nw, uint64_t *chunk_mask,
                                 int32_t *masked_count, int32_t *viewed_count, const double *tile_bounds,
-                                void *stream)
+                                void *stream, const MaskRows *mask_rows = nullptr)
 {
     BFF_REQUIRE(n_points >= 0 && n_pad >= n_points && n_frames >= 0, "bff_project_views: bad sizes");
     BFF_REQUIRE(height > 0 && width > 0, "bff_project_views: bad image size");
@@ -1112,9 +1218,18 @@ static int project_views_launch(const double *xyz, int64_t n_points, int64_t n_p
         BFF_LIMIT(taps_bytes <= 48 * 1024, "bff_project_views_u16: the resize's tap table (12 B per image row and column) "
                   "exceeds 48 KB of LDS: resize in a separate pass (bff_depth_from_u16)");
     }
-    if (maskbits) {
+    if (maskbits || mask_rows) {
         BFF_REQUIRE(word_bits == 32 || word_bits == 64, "bff_project_views: word_bits must be 32 or 64");
         BFF_REQUIRE(frame_mask && frame_rowbase && frame_nmask && rows && n_rows >= 0, "bff_project_views: mask frames need row outputs");
+    }
+    size_t rows_bytes = 0;
+    if (mask_rows) {
+        BFF_REQUIRE(!maskbits && !labels && !segmap, "bff_project_views_lookup: the row directory replaces the decoded planes");
+        BFF_REQUIRE(mask_rows->tab && mask_rows->dir && mask_rows->view_mask_offs, "bff_project_views_lookup: null pointer");
+        BFF_LIMIT(height < (1 << 15) && width < (1 << 15), "bff_project_views_lookup: image too large for packed entries");
+        rows_bytes = sizeof(uint4) * kRowsFrames * kRowsMaskSlots;
+        BFF_LIMIT(taps_bytes + rows_bytes + sizeof(uint64_t) * kBlock * kPPT <= 64 * 1024,
+                  "bff_project_views_lookup: tap table and mask tables exceed 64 KB of LDS");
     }
     const int mw = (int)ceil_div(ceil_div(nw, kCW), 64);
     Intrinsics K;
@@ -1129,16 +1244,29 @@ static int project_views_launch(const double *xyz, int64_t n_points, int64_t n_p
     const hipEvent_t ev0 = g_sweep_start, ev1 = g_sweep_stop;   // attached to the dispatch itself when set
     g_sweep_start = g_sweep_stop = nullptr;
     const RawDepth rd = raw ? *raw : RawDepth{};
+    const MaskRows mr = mask_rows ? *mask_rows : MaskRows{};
+    static_assert(kRowsFrames >= 8, "a block's frame tile must fit the LDS mask tables");
 #define BFF_SWEEP(WORD, LAB, RAW)                                                                                        \
     hipExtLaunchKernelGGL((project_views_kernel<WORD, LAB, RAW>), grid, dim3(kBlock), (unsigned)taps_bytes, as_stream(stream), \
         ev0, ev1, 0,                                                                                                     \
         xyz, n_points, n_pad, inv_pose, K, n_frames, fpb, depth, rd, depth_index, height, width, depth_thresh,           \
         (const WORD *)maskbits, labels, label_stride, segmap, seg_words, frame_mask, frame_rowbase, frame_nmask,        \
-        frame_flags, rows, nw, chunk_mask, mw, masked_count, viewed_count, tile_bounds)
+        frame_flags, rows, nw, chunk_mask, mw, masked_count, viewed_count, tile_bounds, mr)
+#define BFF_SWEEP_ROWS(WORD, RAW)                                                                                        \
+    hipExtLaunchKernelGGL((project_views_kernel<WORD, false, RAW, true>), grid, dim3(kBlock),                            \
+        (unsigned)(taps_bytes + rows_bytes), as_stream(stream), ev0, ev1, 0,                                             \
+        xyz, n_points, n_pad, inv_pose, K, n_frames, fpb, depth, rd, depth_index, height, width, depth_thresh,           \
+        (const WORD *)nullptr, (const uint8_t *)nullptr, label_stride, (const uint32_t *)nullptr, seg_words, frame_mask, \
+        frame_rowbase, frame_nmask, frame_flags, rows, nw, chunk_mask, mw, masked_count, viewed_count, tile_bounds, mr)
 #define BFF_SWEEP_LR(WORD)                                                                                               \
     do { if (labels) { if (raw) BFF_SWEEP(WORD, true, true); else BFF_SWEEP(WORD, true, false); }                        \
          else { if (raw) BFF_SWEEP(WORD, false, true); else BFF_SWEEP(WORD, false, false); } } while (0)
-    if (!maskbits || word_bits == 32) BFF_SWEEP_LR(uint32_t); else BFF_SWEEP_LR(uint64_t);
+    if (mask_rows) {
+        if (word_bits == 32) { if (raw) BFF_SWEEP_ROWS(uint32_t, true); else BFF_SWEEP_ROWS(uint32_t, false); }
+        else { if (raw) BFF_SWEEP_ROWS(uint64_t, true); else BFF_SWEEP_ROWS(uint64_t, false); }
+    }
+    else if (!maskbits || word_bits == 32) BFF_SWEEP_LR(uint32_t); else BFF_SWEEP_LR(uint64_t);
+#undef BFF_SWEEP_ROWS
 #undef BFF_SWEEP_LR
 #undef BFF_SWEEP
     return launched("bff_project_views");
@@ -1181,6 +1309,33 @@ extern "C" int bff_project_views_u16(const double *xyz, int64_t n_points, int64_
                                 width, depth_thresh, maskbits, labels, segmap, word_bits, frame_mask, frame_rowbase,
                                 frame_nmask, frame_flags, rows, n_rows, nw, chunk_mask, masked_count, viewed_count,
                                 tile_bounds, stream);
+}
+
+extern "C" int bff_project_views_lookup(const double *xyz, int64_t n_points, int64_t n_pad,
+                                        const double *inv_pose, const double *cam_intr_host, int32_t n_frames,
+                                        const void *depth, int32_t depth_h, int32_t depth_w, int32_t depth_layout,
+                                        const int32_t *depth_index, int32_t height, int32_t width, double depth_thresh,
+                                        const uint32_t *mask_tab, const uint32_t *mask_dir, const int32_t *run_start,
+                                        const int32_t *run_end, const int32_t *view_mask_offs, int32_t word_bits,
+                                        const int32_t *frame_mask, const int32_t *frame_rowbase, const int32_t *frame_nmask,
+                                        const int32_t *frame_flags,
+                                        uint64_t *rows, int64_t n_rows, int64_t nw, uint64_t *chunk_mask,
+                                        int32_t *masked_count, int32_t *viewed_count, const double *tile_bounds,
+                                        void *stream)
+{
+    BFF_REQUIRE(depth_layout >= -1 && depth_layout <= 2, "bff_project_views_lookup: depth_layout must be -1, 0, 1 or 2");
+    if (n_points == 0 || n_frames == 0) return BFF_OK;
+    BFF_REQUIRE(height > 0 && width > 0, "bff_project_views_lookup: bad image size");
+    const MaskRows mr{reinterpret_cast<const uint4 *>(mask_tab), mask_dir, run_start, run_end, view_mask_offs};
+    RawDepth raw;
+    if (depth_layout >= 0) {
+        const int rc = raw_depth_params(depth_h, depth_w, height, width, depth_layout, as_stream(stream), &raw);
+        if (rc != BFF_OK) return rc;
+    }
+    return project_views_launch(xyz, n_points, n_pad, inv_pose, cam_intr_host, n_frames, depth, depth_layout >= 0 ? &raw : nullptr,
+                                depth_index, height, width, depth_thresh, nullptr, nullptr, nullptr, word_bits, frame_mask,
+                                frame_rowbase, frame_nmask, frame_flags, rows, n_rows, nw, chunk_mask, masked_count,
+                                viewed_count, tile_bounds, stream, &mr);
 }
 
 extern "C" int bff_count_viewed(const double *xyz, int64_t n_points, int64_t n_pad, const double *inv_pose,

@@ -69,6 +69,7 @@ extern "C" int bff_scene_project_viewed(const bff_scene *sc, const bff_scene_par
     const int n_rows = sc->n_rows, cap = ws->group_cap;
     BFF_REQUIRE(cap == BFF_GROUP_CAP || cap == BFF_GROUP_CAP_MAX, "bff_scene_project: group_cap must be %d or %d", BFF_GROUP_CAP, BFF_GROUP_CAP_MAX);
     const int mw = bff_chunk_mask_words(nw);
+    const bool lookup = bff_mask_lookup_rows(sc->height, sc->width, n_rows) != 0;     // masks looked up row by row, not decoded
     int32_t *hdr = ws->hdr;
     hipError_t e;
 #define BFF_ZERO(ptr, bytes) do { e = hipMemsetAsync((ptr), 0, (bytes), st); \
@@ -88,7 +89,7 @@ extern "C" int bff_scene_project_viewed(const bff_scene *sc, const bff_scene_par
         const bool use_cpop = bff_merge_uses_chunk_bound(nw) != 0;
         BFF_REQUIRE(inside(ws->masked, sizeof(int32_t) * (size_t)n) && inside(ws->viewed, sizeof(int32_t) * (size_t)n) &&
                     inside(ws->count, sizeof(int32_t) * (size_t)n_rows) &&
-                    inside(ws->chunk_mask, sizeof(uint64_t) * (size_t)n_rows * mw) && inside(ws->segmap, seg_bytes) &&
+                    inside(ws->chunk_mask, sizeof(uint64_t) * (size_t)n_rows * mw) && (lookup || inside(ws->segmap, seg_bytes)) &&
                     inside(hdr, sizeof(int32_t) * (size_t)bff_scene_header_words(sc->s1_rows, cap)) &&
                     inside(ws->agg, sizeof(uint64_t) * (size_t)cap * nw) &&
                     inside(ws->merge_scratch, sizeof(uint32_t) * (size_t)bff_merge_scratch_words(n_rows)) &&
@@ -114,16 +115,30 @@ extern "C" int bff_scene_project_viewed(const bff_scene *sc, const bff_scene_par
         BFF_REQUIRE(ws->events[0] && ws->events[1] && ws->events[2] && ws->events[3], "bff_scene_project: a heavy stream needs the workspace's four events");
         BFF_TRY(hand_over(ws->events[0], stream, hv));
     }
-    // a1: 2-D RLE -> label plane (+ words where masks overlap, + segment bitmap)
-    BFF_TRY(bff_rle_to_labels(sc->run_start, sc->run_end, sc->mask_run_offs, sc->view_mask_offs, sc->n_mviews, hw,
-                              sc->word_bits, ws->labels, ws->maskbits, ws->segmap, hv));
+    // a1: 2-D RLE -> the masks' row directory, or the label plane (+ words where masks overlap, + segment bitmap)
+    if (lookup) {
+        BFF_REQUIRE(ws->mask_tab && ws->mask_dir, "bff_scene_project: no row directory buffers");
+        BFF_TRY(bff_mask_row_directory(sc->run_start, sc->run_end, sc->mask_run_offs, n_rows, sc->height, sc->width,
+                                       ws->mask_tab, ws->mask_dir, hv));
+    } else {
+        BFF_TRY(bff_rle_to_labels(sc->run_start, sc->run_end, sc->mask_run_offs, sc->view_mask_offs, sc->n_mviews, hw,
+                                  sc->word_bits, ws->labels, ws->maskbits, ws->segmap, hv));
+    }
     // a2-a8 (+a15): the fused sweep.  ws->rows is all zero on entry (and again on exit, see below)
     const bool ratio = pr->filter_mode == 2;
     // the detection ratio's denominator: counted by this sweep (frames with flag bit 0), or given by the caller
     // (bff_count_viewed over the scene's viewed frames, shared by the classes of the scene)
     int32_t *const sweep_viewed = (ratio && !viewed_in) ? ws->viewed : nullptr;
     const int32_t *const viewed = ratio ? (viewed_in ? viewed_in : ws->viewed) : nullptr;
-    if (sc->depth_raw)          // depth as the PNGs store it: /1000 + bilinear resize per point inside the sweep
+    if (lookup)
+        BFF_TRY(bff_project_views_lookup(sc->xyz, n, sc->n_pad, sc->inv_pose, sc->cam_intr, sc->n_frames,
+                                         sc->depth_raw ? sc->depth_raw : (const void *)sc->depth, sc->depth_h, sc->depth_w,
+                                         sc->depth_raw ? sc->depth_tiled : -1, sc->depth_index, sc->height, sc->width,
+                                         pr->depth_thresh, ws->mask_tab, ws->mask_dir, sc->run_start, sc->run_end,
+                                         sc->view_mask_offs, sc->word_bits, sc->frame_mask, sc->frame_rowbase, sc->frame_nmask,
+                                         sc->frame_flags, ws->rows, n_rows, nw, ws->chunk_mask, ws->masked, sweep_viewed,
+                                         sc->tile_bounds, hv));
+    else if (sc->depth_raw)     // depth as the PNGs store it: /1000 + bilinear resize per point inside the sweep
         BFF_TRY(bff_project_views_u16(sc->xyz, n, sc->n_pad, sc->inv_pose, sc->cam_intr, sc->n_frames, sc->depth_raw,
                                       sc->depth_h, sc->depth_w, sc->depth_tiled, sc->depth_index, sc->height, sc->width, pr->depth_thresh,
                                       ws->maskbits, ws->labels, ws->segmap, sc->word_bits, sc->frame_mask, sc->frame_rowbase,

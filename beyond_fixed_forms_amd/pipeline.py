@@ -50,7 +50,7 @@ class ParamsStruct(ctypes.Structure):
 _WS_PTRS = ["maskbits", "segmap", "labels", "rows", "chunk_mask", "keep", "tile_mask", "agg", "both",
             "masked", "viewed", "sel_scratch", "area", "mean_word", "order", "parent", "comp", "count",
             "gmembers", "goffs", "slices", "pair_scratch", "vals", "vals_sorted", "hist", "merge_scratch", "chunk_pop",
-            "sig", "sig_keys", "sig_sorted", "sort_temp"]
+            "sig", "sig_keys", "sig_sorted", "sort_temp", "mask_tab", "mask_dir"]
 
 
 class WorkspaceStruct(ctypes.Structure):
@@ -243,13 +243,20 @@ class SceneWorkspace:
         mw = max(lib.bff_chunk_mask_words(nw), 1)
         nt = (n_rows + 63) // 64
         i32, i64, f32 = torch.int32, torch.int64, torch.float32
-        self._need("maskbits", n_mviews * hw * (1 if ds.word_bits == 32 else 2), i32)
-        self._need("labels", n_mviews * int(lib.bff_label_plane_stride(hw)), torch.uint8)
+        # the masks' row directory (16 B per mask + 4 B per mask and image row) replaces the decoded planes (4 or 8 B of mask
+        # words + 1 B of palette blocks per pixel of every mask view) wherever the library looks masks up (BFF_MASK_LOOKUP)
+        lookup = _lib.mask_lookup_rows(ds.height, ds.width, n_rows)
+        if lookup:
+            self._need("mask_tab", 4 * (n_rows + 1), i32)
+            self._need("mask_dir", n_rows * ds.height, i32)
+        else:
+            self._need("maskbits", n_mviews * hw * (1 if ds.word_bits == 32 else 2), i32)
+            self._need("labels", n_mviews * int(lib.bff_label_plane_stride(hw)), torch.uint8)
         if self._need("rows", n_rows * nw, i64, zero=True):
             self.rows_dirty = False
         # everything the call's steps expect zeroed lives in ONE allocation, cleared by one fill per scene
         # (bff_scene_workspace): name -> (bytes, dtype of the view)
-        seg_words = 2 * n_mviews * _lib.segmap_words(hw)
+        seg_words = 0 if lookup else 2 * n_mviews * _lib.segmap_words(hw)
         hdr_words = int(lib.bff_scene_header_words(s1_rows, cap))
         use_cpop = bool(lib.bff_merge_uses_chunk_bound(nw))
         parts = [("masked", 4 * n, i32), ("viewed", 4 * n, i32), ("count", 4 * n_rows, i32),

@@ -32,7 +32,7 @@ extern "C" {
 #define BFF_E_ARG (-1)      /* null pointer / negative size / unsupported parameter */
 #define BFF_E_LIMIT (-2)    /* size beyond what a kernel supports (documented per call) */
 
-#define BFF_ABI_VERSION 11
+#define BFF_ABI_VERSION 12
 
 int bff_abi_version(void);
 const char *bff_last_error(void);
@@ -596,6 +596,38 @@ int bff_cross_popcount_dev(const uint64_t *a, int32_t na, const uint64_t *b, int
 int bff_clear_flagged_chunks_unless(uint64_t *rows, int32_t n_rows, int64_t nw, const uint64_t *chunk_mask,
                                     const int32_t *veto, void *stream);
 
+/* Row directory of the 2-D masks: what the sweep's look-up mode (bff_project_views_lookup) asks instead of a decoded
+ * image.  Inputs: the run tables of bff_rle_to_maskbits (per mask sorted, disjoint, non-empty runs inside
+ * [0, height * width)) for n_masks masks.  Outputs (formats: beyond_fixed_forms_amd/csrc/mask_rows.h):
+ *   mask_tab  uint32 [n_masks + 1][4], 16-byte aligned: per mask its box (c0 | R0 << 16, c1 | R1 << 16; R0 / R1 the rows of
+ *             its first / last pixel, c0 / c1 the smallest / largest column a run touches, full width when a run crosses
+ *             a row end; a mask without runs: 0xffffffff, 0), dir_offs (exclusive scan of the boxes' heights, computed on the
+ *             device) and its first run; entry n_masks closes the table with the totals
+ *   mask_dir  uint32, capacity n_masks * height: one entry per row of every box for the runs that intersect the row --
+ *             0 (none), cs | ce << 15 (one run, clipped to the row), or 1 << 31 | count << 27 | first run relative to the
+ *             mask, count saturated at 15 = "search from there to the mask's last run"
+ * width, height < 2^15.  Deterministic: every word depends on the run tables only. */
+int bff_mask_row_directory(const int32_t *run_start, const int32_t *run_end, const int32_t *mask_run_offs,
+                           int32_t n_masks, int32_t height, int32_t width, uint32_t *mask_tab, uint32_t *mask_dir,
+                           void *stream);
+/* 1: bff_scene_project looks masks up in the row directory for images of this size with n_masks masks in all; 0: it decodes
+ * them (BFF_MASK_LOOKUP=dense, read once per process, or an image the packed entries / the sweep's LDS do not hold). */
+int32_t bff_mask_lookup_rows(int32_t height, int32_t width, int64_t n_masks);
+/* bff_project_views / bff_project_views_u16 with the masks looked up in the row directory: same outputs, bit for bit, for
+ * run tables under the contract above.  depth_layout -1: `depth` is float32 [n_depth][height * width] (depth_h / depth_w
+ * unused), else as bff_project_views_u16.  view_mask_offs names a frame's masks (frame_mask[f] indexes it). */
+int bff_project_views_lookup(const double *xyz, int64_t n_points, int64_t n_pad,
+                             const double *inv_pose, const double *cam_intr_host, int32_t n_frames,
+                             const void *depth, int32_t depth_h, int32_t depth_w, int32_t depth_layout,
+                             const int32_t *depth_index, int32_t height, int32_t width, double depth_thresh,
+                             const uint32_t *mask_tab, const uint32_t *mask_dir, const int32_t *run_start,
+                             const int32_t *run_end, const int32_t *view_mask_offs, int32_t word_bits,
+                             const int32_t *frame_mask, const int32_t *frame_rowbase, const int32_t *frame_nmask,
+                             const int32_t *frame_flags,
+                             uint64_t *rows, int64_t n_rows, int64_t nw, uint64_t *chunk_mask,
+                             int32_t *masked_count, int32_t *viewed_count, const double *tile_bounds,
+                             void *stream);
+
 /* Device-resident inputs of one scene (what scene.prepare_scene uploads; all pointers are device pointers). */
 typedef struct bff_scene {
     int64_t n_points, n_pad, nw;
@@ -627,6 +659,8 @@ typedef struct bff_scene_params {
 
 /* Scratch of bff_scene_project, allocated by the caller for the scene's sizes (beyond_fixed_forms_amd/pipeline.py).
  * `rows` must be all zero on entry; it is all zero again when the call's work has run on the fast path.
+ * Masks are looked up in the row directory (mask_tab, mask_dir) when bff_mask_lookup_rows(height, width, n_rows) says so;
+ * then maskbits, labels and segmap are not used and may be NULL.  Otherwise the directory buffers may be NULL.
  * Every buffer the call's steps expect zeroed -- masked, viewed, count, chunk_mask, segmap, hdr, agg, merge_scratch
  * and (clouds that use the chunk bound) chunk_pop -- must lie inside ONE allocation of `zero_bytes` bytes
  * starting at `masked`: the call clears it with a single fill (checked; beyond_fixed_forms_amd/pipeline.py lays it out). */
@@ -641,7 +675,9 @@ typedef struct bff_scene_workspace {
     uint32_t *hist, *merge_scratch;
     uint16_t *chunk_pop;            /* [n_rows][64 * chunk-mask words] */
     int64_t *sig, *sig_keys, *sig_sorted;
-    void *sort_temp; size_t sort_temp_bytes;
+    void *sort_temp;
+    uint32_t *mask_tab, *mask_dir;  /* bff_mask_row_directory: [n_rows + 1][4] and n_rows * height words */
+    size_t sort_temp_bytes;
     size_t zero_bytes;              /* size of the block that starts at `masked` (see above) */
     int32_t *hdr;                   /* device, bff_scene_header_words(s1_rows, group_cap) int32 */
     int32_t *hdr_host;              /* pinned host mirror of the same size */
