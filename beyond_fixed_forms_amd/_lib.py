@@ -34,6 +34,7 @@ SIGNATURES = {
     "bff_count_viewed": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _I, _P, _P, _P],
     "bff_render_depth_u16": [_P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "bff_render_mesh_depth_u16": [_P, _L, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "bff_render_mesh_depth_clip_u16": [_P, _L, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _D, _I, _P, _P, _P],
     "bff_popcount_rows": [_P, _P, _I, _L, _P, _P],
     "bff_cross_popcount": [_P, _P, _I, _P, _P, _I, _L, _P, _P],
     "bff_row_stats": [_P, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P],
@@ -89,7 +90,7 @@ PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, [
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class BffLibraryError(RuntimeError):
@@ -388,14 +389,18 @@ def render_depth(xyz_soa, n_points, inv_pose, cam_intr, height, width, depth_h, 
 
 
 def render_mesh_depth(vertices_soa, n_vertices, faces, inv_pose, cam_intr, height, width, depth_h, depth_w,
-                      frames_per_block=0, scratch_texels=None):
+                      frames_per_block=0, scratch_texels=None, near_clip=0.0):
     """Depth frames out of a triangle mesh (bff_render_mesh_depth_u16): vertices_soa f64 [3][nv_pad], faces int32 [T][3]
     on the same device with every index in [0, n_vertices) (validated by the caller: scene.checked_faces).  A texel of
     frame f holds the nearest covering triangle's interpolated depth in millimetres at the texel's sample point, 0 =
     none (the definition is the header's).  -> int16 [F][depth_h][depth_w], on the current launch stream.  Scratch cap
-    and frame runs are render_depth's (each run reads the mesh once more)."""
+    and frame runs are render_depth's (each run reads the mesh once more).  near_clip: 0 = a triangle that reaches behind
+    the camera plane is dropped; a value in (0, 65.535) metres = it is clipped at that depth instead
+    (bff_render_mesh_depth_clip_u16; anything else is rejected by the library)."""
     if faces.dtype != i32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
         raise ValueError("render_mesh_depth: faces must be a contiguous int32 [T][3] tensor")
+    near_clip = float(near_clip)
+    clip = near_clip != 0.0                                    # NaN included: the library rejects it
     k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
     f, plane = int(inv_pose.shape[0]), int(depth_h) * int(depth_w)
     out = torch.empty((f, int(depth_h), int(depth_w)), dtype=torch.int16, device=vertices_soa.device)
@@ -403,9 +408,13 @@ def render_mesh_depth(vertices_soa, n_vertices, faces, inv_pose, cam_intr, heigh
     scratch = torch.empty(max(per * plane, 1), dtype=i32, device=vertices_soa.device)
     for f0 in range(0, max(f, 1), per):
         f1 = min(f, f0 + per)
-        call("bff_render_mesh_depth_u16", _ptr(vertices_soa, f64), int(n_vertices), vertices_soa.shape[1], _ptr(faces),
-             int(faces.shape[0]), _ptr(inv_pose[f0:f1], f64), ctypes.cast(k, c_void_p), f1 - f0, int(height), int(width),
-             int(depth_h), int(depth_w), int(frames_per_block), _ptr(scratch), _ptr(out[f0:f1]))
+        head = (_ptr(vertices_soa, f64), int(n_vertices), vertices_soa.shape[1], _ptr(faces), int(faces.shape[0]),
+                _ptr(inv_pose[f0:f1], f64), ctypes.cast(k, c_void_p), f1 - f0, int(height), int(width), int(depth_h), int(depth_w))
+        tail = (int(frames_per_block), _ptr(scratch), _ptr(out[f0:f1]))
+        if clip:
+            call("bff_render_mesh_depth_clip_u16", *head, near_clip, *tail)
+        else:
+            call("bff_render_mesh_depth_u16", *head, *tail)
     return out
 
 

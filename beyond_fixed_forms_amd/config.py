@@ -24,6 +24,10 @@ DEFAULTS = dict(
     # (scene_mesh_dir/<scene_id>.npz: `faces` (T, 3) integers, optionally `vertices` (V, 3); without them the faces index the
     # rows of <scene_id>.npy).  0 = off; setting both keys is an error
     depth_from_mesh=0, scene_mesh_dir=None,
+    # not a key of the reference either: metres.  With depth_from_mesh on, a triangle that reaches nearer than this (or
+    # behind the camera) is clipped at this depth instead of dropped whole (scene.mesh_near_clip); 0 = off, the frames as
+    # they were.  0.05 is a starting value nobody has tuned
+    mesh_near_clip=0.0,
 )
 
 

@@ -240,6 +240,165 @@ __global__ __launch_bounds__(kRmBlock) void render_mesh_depth_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same with a near plane (bff_render_mesh_depth_clip_u16).  One thread owns one triangle; per frame it also keeps c0
+// and c1 of its vertices, cuts the triangle at c2 = zn into a polygon of up to four screen vertices (named registers),
+// and sends the fan's one or two triangles through raster_tri.  A clipped wall beside the camera usually covers the
+// frame: the wave walk is the common case here.
+
+// camera_point with c0 and c1 kept: the cut points are formed in camera coordinates
+__device__ __forceinline__ void camera_point(const double *__restrict__ P, const CameraK &K, double x, double y, double z,
+                                             double &c0, double &c1, double &c2, double &px, double &py)
+{
+    c0 = fma(P[3], 1.0, fma(P[2], z, fma(P[1], y, fma(P[0], x, 0.0))));
+    c1 = fma(P[7], 1.0, fma(P[6], z, fma(P[5], y, fma(P[4], x, 0.0))));
+    c2 = fma(P[11], 1.0, fma(P[10], z, fma(P[9], y, fma(P[8], x, 0.0))));
+    px = __dadd_rn(__dadd_rn(__dmul_rn(K.k[0], c0), __dmul_rn(K.k[1], c1)), __dmul_rn(K.k[2], c2)) / c2;
+    py = __dadd_rn(__dadd_rn(__dmul_rn(K.k[3], c0), __dmul_rn(K.k[4], c1)), __dmul_rn(K.k[5], c2)) / c2;
+}
+
+struct CamVtx { double c0, c1, c2, px, py; };                      // a vertex in camera coordinates and on the screen
+
+__device__ __forceinline__ bool in_pixel_range(const ScreenTri &t)
+{
+    return fabs(t.x0) < kRmPixelLimit && fabs(t.x1) < kRmPixelLimit && fabs(t.x2) < kRmPixelLimit &&
+           fabs(t.y0) < kRmPixelLimit && fabs(t.y1) < kRmPixelLimit && fabs(t.y2) < kRmPixelLimit;
+}
+
+// render_mesh_depth_kernel's box, lane walk and wave walk for one screen triangle per lane (that kernel keeps its own
+// lines: called from there, this function changed its machine code).  Every lane of the wave comes here (takes = false:
+// it has nothing to draw): the wave walk needs them all at its ballot.
+__device__ __forceinline__ void raster_tri(const ScreenTri &t, bool takes, int lane, double sx, double sy, int H, int W,
+                                           int dh, int dw, uint32_t *__restrict__ img)
+{
+    TexelBox b = {0, 0, 0, 0};
+    // two vertices at one position: e0 + e1 + e2 is exactly 0 at every texel (one e is x * y - x * y, the other two
+    // are each other's negatives), so nothing is covered
+    const bool flat = (t.x0 == t.x1 && t.y0 == t.y1) || (t.x1 == t.x2 && t.y1 == t.y2) || (t.x0 == t.x2 && t.y0 == t.y2);
+    if (takes && !flat) {
+        const double xlo = fmin(t.x0, fmin(t.x1, t.x2)), xhi = fmax(t.x0, fmax(t.x1, t.x2));
+        const double ylo = fmin(t.y0, fmin(t.y1, t.y2)), yhi = fmax(t.y0, fmax(t.y1, t.y2));
+        int j1, i1;
+        texel_range(xlo, xhi, sx, dw, b.j0, j1);
+        texel_range(ylo, yhi, sy, dh, b.i0, i1);
+        // The box must hold every texel the header's arithmetic covers.  A texel outside it lies more than a texel
+        // beyond the vertices along x (or y): x_k - X has one sign for all k, the sample point is outside the
+        // triangle, and the negative edge functions add up to at least |A| * sx / ex (A: twice the area, ex >= |x_k -
+        // X|).  Rounding can lift an edge function to >= 0 only from above -2^-52 ex ey, so the texel can pass as
+        // covered only where |A| <= 2^-51 ex ey (ex / sx); with the rounding of A itself, 2^-49 ex ey max(ex / sx, ey /
+        // sy) bounds it.  Such a sliver (three distinct vertices on a line) takes the whole frame as its box.
+        const double ex = fmax(fabs(xlo), fabs(xhi)) + (double)W, ey = fmax(fabs(ylo), fabs(yhi)) + (double)H;
+        const double A = (t.x1 - t.x0) * (t.y2 - t.y0) - (t.x2 - t.x0) * (t.y1 - t.y0);
+        if (!(fabs(A) > 0x1p-49 * ex * ey * fmax(ex / sx, ey / sy)))
+            b.j0 = 0, j1 = dw - 1, b.i0 = 0, i1 = dh - 1;
+        if (j1 >= b.j0 && i1 >= b.i0) {
+            b.bw = j1 - b.j0 + 1;
+            b.count = b.bw * (i1 - b.i0 + 1);                  // <= dh * dw < 2^31
+        }
+    }
+    if (b.count > 0 && b.count <= kRmLaneBox)                  // the lane's own walk, row by row
+        for (int k = 0, i = b.i0, j = b.j0; k < b.count; ++k) {
+            mesh_texel(t, i, j, sx, sy, dw, img);
+            if (++j == b.j0 + b.bw) j = b.j0, ++i;
+        }
+    uint64_t big = __ballot(b.count > kRmLaneBox);             // every lane of the wave is here: no early exit above
+    while (big) {
+        const int src = __ffsll((unsigned long long)big) - 1;
+        big &= big - 1;
+        ScreenTri w;
+        w.x0 = __shfl(t.x0, src), w.y0 = __shfl(t.y0, src), w.r0 = __shfl(t.r0, src);
+        w.x1 = __shfl(t.x1, src), w.y1 = __shfl(t.y1, src), w.r1 = __shfl(t.r1, src);
+        w.x2 = __shfl(t.x2, src), w.y2 = __shfl(t.y2, src), w.r2 = __shfl(t.r2, src);
+        const int wj0 = __shfl(b.j0, src), wi0 = __shfl(b.i0, src), wbw = __shfl(b.bw, src), wcount = __shfl(b.count, src);
+        for (unsigned k = lane; k < (unsigned)wcount; k += kWave)           // unsigned: wcount + 63 may pass 2^31
+            mesh_texel(w, wi0 + (int)(k / (unsigned)wbw), wj0 + (int)(k % (unsigned)wbw), sx, sy, dw, img);
+    }
+}
+
+// The clipped polygon: up to four screen vertices in named registers (no indexed array: that would live in scratch
+// memory).  emit: the next vertex goes into the first free slot; a polygon never has a fifth
+struct Polygon {
+    double x0, y0, r0, x1, y1, r1, x2, y2, r2, x3, y3, r3;
+    int n;
+    __device__ __forceinline__ void emit(double x, double y, double r)
+    {
+        x0 = n == 0 ? x : x0, y0 = n == 0 ? y : y0, r0 = n == 0 ? r : r0;
+        x1 = n == 1 ? x : x1, y1 = n == 1 ? y : y1, r1 = n == 1 ? r : r1;
+        x2 = n == 2 ? x : x2, y2 = n == 2 ? y : y2, r2 = n == 2 ? r : r2;
+        x3 = n == 3 ? x : x3, y3 = n == 3 ? y : y3, r3 = n == 3 ? r : r3;
+        ++n;
+    }
+};
+
+// Edge a -> b of the header's polygon walk: a itself when it is inside, and the cut point when the edge crosses the near
+// plane, computed from the inside vertex towards the outside one whichever way the edge is walked
+__device__ __forceinline__ void clip_edge(const CamVtx &a, bool a_in, const CamVtx &b, bool b_in, const CameraK &K, double zn,
+                                          double rn, Polygon &q)
+{
+    if (a_in) q.emit(a.px, a.py, 1.0 / a.c2);
+    if (a_in != b_in) {
+        const double p0 = a_in ? a.c0 : b.c0, p1 = a_in ? a.c1 : b.c1, p2 = a_in ? a.c2 : b.c2;
+        const double o0 = a_in ? b.c0 : a.c0, o1 = a_in ? b.c1 : a.c1, o2 = a_in ? b.c2 : a.c2;
+        const double t = __dsub_rn(p2, zn) / __dsub_rn(p2, o2);
+        const double i0 = __dadd_rn(p0, __dmul_rn(t, __dsub_rn(o0, p0)));
+        const double i1 = __dadd_rn(p1, __dmul_rn(t, __dsub_rn(o1, p1)));
+        const double x = __dadd_rn(__dadd_rn(__dmul_rn(K.k[0], i0), __dmul_rn(K.k[1], i1)), __dmul_rn(K.k[2], zn)) / zn;
+        const double y = __dadd_rn(__dadd_rn(__dmul_rn(K.k[3], i0), __dmul_rn(K.k[4], i1)), __dmul_rn(K.k[5], zn)) / zn;
+        q.emit(x, y, rn);
+    }
+}
+
+__device__ __forceinline__ bool finite3(const CamVtx &v) { return isfinite(v.c0) && isfinite(v.c1) && isfinite(v.c2); }
+
+__global__ __launch_bounds__(kRmBlock) void render_mesh_depth_clip_kernel(
+    const double *__restrict__ vtx, int64_t n_vertices, int64_t nv_pad, const int32_t *__restrict__ faces, int64_t n_faces,
+    const double *__restrict__ inv_pose, CameraK K, int n_frames, int frames_per_block, int H, int W, int dh, int dw,
+    double zn, uint32_t *__restrict__ scratch)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t tri = (int64_t)blockIdx.x * kRmBlock + threadIdx.x;
+    const int f0 = blockIdx.y * frames_per_block;
+    const int f1 = min(n_frames, f0 + frames_per_block);
+    const int64_t plane = (int64_t)dh * dw;
+    const double sx = (double)W / (double)dw, sy = (double)H / (double)dh;
+
+    // the caller has validated the indices; a triangle that names a vertex outside the array is still never read
+    bool valid = tri < n_faces;
+    int64_t v0 = 0, v1 = 0, v2 = 0;
+    if (valid) {
+        v0 = faces[3 * tri], v1 = faces[3 * tri + 1], v2 = faces[3 * tri + 2];
+        valid = v0 >= 0 && v0 < n_vertices && v1 >= 0 && v1 < n_vertices && v2 >= 0 && v2 < n_vertices;
+        if (!valid) v0 = v1 = v2 = 0;
+    }
+    const double ax = vtx[v0], ay = vtx[nv_pad + v0], az = vtx[2 * nv_pad + v0];
+    const double bx = vtx[v1], by = vtx[nv_pad + v1], bz = vtx[2 * nv_pad + v1];
+    const double cx = vtx[v2], cy = vtx[nv_pad + v2], cz = vtx[2 * nv_pad + v2];
+
+    for (int f = f0; f < f1; ++f) {                                // wave-uniform
+        const double *P = inv_pose + 16 * (int64_t)f;
+        uint32_t *img = scratch + (int64_t)f * plane;
+        CamVtx a, b, c;
+        camera_point(P, K, ax, ay, az, a.c0, a.c1, a.c2, a.px, a.py);
+        camera_point(P, K, bx, by, bz, b.c0, b.c1, b.c2, b.px, b.py);
+        camera_point(P, K, cx, cy, cz, c.c0, c.c1, c.c2, c.px, c.py);
+        const bool part = valid && finite3(a) && finite3(b) && finite3(c);
+        const bool a_in = part && a.c2 >= zn, b_in = part && b.c2 >= zn, c_in = part && c.c2 >= zn;
+        const double rn = 1.0 / zn;
+        Polygon q = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0};      // 0, 3 or 4 vertices, in the
+        clip_edge(a, a_in, b, b_in, K, zn, rn, q);                                        // header's emission order
+        clip_edge(b, b_in, c, c_in, K, zn, rn, q);
+        clip_edge(c, c_in, a, a_in, K, zn, rn, q);
+        // the fan (q0, q1, q2), (q0, q2, q3); the second pass only where a lane of the wave has a quadrilateral
+        for (int pass = 0; pass < 2; ++pass) {                 // wave-uniform: every lane reaches raster_tri's ballot
+            if (pass == 1 && !__any(q.n == 4)) break;
+            const ScreenTri t = {q.x0, q.y0, q.r0, pass ? q.x2 : q.x1, pass ? q.y2 : q.y1, pass ? q.r2 : q.r1,
+                                 pass ? q.x3 : q.x2, pass ? q.y3 : q.y2, pass ? q.r3 : q.r2};
+            const bool takes = (pass ? q.n == 4 : q.n >= 3) && in_pixel_range(t);
+            raster_tri(t, takes, lane, sx, sy, H, W, dh, dw, img);
+        }
+    }
+}
+
 // the scratch of a render call -> its uint16 frames
 static int narrow_frames(const uint32_t *scratch_u32, int64_t total, uint16_t *out_u16, hipStream_t st, const char *what)
 {
@@ -300,33 +459,34 @@ extern "C" int bff_render_depth_u16(const double *xyz, int64_t n_points, int64_t
 
 extern "C" int bff_mesh_lane_box(void) { return kRmLaneBox; }
 
-extern "C" int bff_render_mesh_depth_u16(const double *vertices, int64_t n_vertices, int64_t nv_pad, const int32_t *faces,
-                                         int64_t n_faces, const double *inv_pose, const double *cam_intr_host,
-                                         int32_t n_frames, int32_t height, int32_t width, int32_t depth_h, int32_t depth_w,
-                                         int32_t frames_per_block, uint32_t *scratch_u32, uint16_t *out_u16, void *stream)
+// both mesh entry points: the checks, the early returns, the fill of the scratch, one of the two kernels, the narrowing
+static int render_mesh(const char *what, bool clip, double near_clip, const double *vertices, int64_t n_vertices,
+                       int64_t nv_pad, const int32_t *faces, int64_t n_faces, const double *inv_pose,
+                       const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width, int32_t depth_h,
+                       int32_t depth_w, int32_t frames_per_block, uint32_t *scratch_u32, uint16_t *out_u16, void *stream)
 {
     BFF_REQUIRE(n_vertices >= 0 && nv_pad >= n_vertices && n_faces >= 0 && n_frames >= 0 && frames_per_block >= 0,
-                "bff_render_mesh_depth_u16: bad sizes");
-    BFF_REQUIRE(height > 0 && width > 0 && depth_h > 0 && depth_w > 0, "bff_render_mesh_depth_u16: bad image size");
-    BFF_LIMIT((int64_t)height * width < (1ll << 31), "bff_render_mesh_depth_u16: image larger than 2^31 pixels");
-    BFF_LIMIT((int64_t)depth_h * depth_w < (1ll << 31), "bff_render_mesh_depth_u16: depth frame larger than 2^31 texels");
+                "%s: bad sizes", what);
+    BFF_REQUIRE(height > 0 && width > 0 && depth_h > 0 && depth_w > 0, "%s: bad image size", what);
+    BFF_LIMIT((int64_t)height * width < (1ll << 31), "%s: image larger than 2^31 pixels", what);
+    BFF_LIMIT((int64_t)depth_h * depth_w < (1ll << 31), "%s: depth frame larger than 2^31 texels", what);
     BFF_LIMIT((int64_t)height * depth_h < (1ll << 31) && (int64_t)width * depth_w < (1ll << 31),
-              "bff_render_mesh_depth_u16: pixel x texel products beyond 2^31 (height * depth_h, width * depth_w)");
-    BFF_LIMIT(n_frames <= 65535, "bff_render_mesh_depth_u16: too many frames");
-    BFF_LIMIT(n_faces < (1ll << 31), "bff_render_mesh_depth_u16: 2^31 triangles or more");
+              "%s: pixel x texel products beyond 2^31 (height * depth_h, width * depth_w)", what);
+    BFF_LIMIT(n_frames <= 65535, "%s: too many frames", what);
+    BFF_LIMIT(n_faces < (1ll << 31), "%s: 2^31 triangles or more", what);
     const int64_t total = (int64_t)n_frames * depth_h * depth_w;
-    BFF_LIMIT(ceil_div(ceil_div(total, 4), 256) < (1ll << 31), "bff_render_mesh_depth_u16: too many texels for one launch");
+    BFF_LIMIT(ceil_div(ceil_div(total, 4), 256) < (1ll << 31), "%s: too many texels for one launch", what);
     if (n_frames == 0) return BFF_OK;
-    BFF_REQUIRE(out_u16, "bff_render_mesh_depth_u16: null pointer");
+    BFF_REQUIRE(out_u16, "%s: null pointer", what);
     hipStream_t st = as_stream(stream);
     if (n_faces == 0 || n_vertices == 0) {                           // nothing is drawn: every texel is "no depth"
         hipError_t e = hipMemsetAsync(out_u16, 0, sizeof(uint16_t) * (size_t)total, st);
-        if (e != hipSuccess) return fail((int)e, "bff_render_mesh_depth_u16: memset: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail((int)e, "%s: memset: %s", what, hipGetErrorString(e));
         return BFF_OK;
     }
-    BFF_REQUIRE(vertices && faces && inv_pose && cam_intr_host && scratch_u32, "bff_render_mesh_depth_u16: null pointer");
+    BFF_REQUIRE(vertices && faces && inv_pose && cam_intr_host && scratch_u32, "%s: null pointer", what);
     hipError_t e = hipMemsetAsync(scratch_u32, 0xff, sizeof(uint32_t) * (size_t)total, st);
-    if (e != hipSuccess) return fail((int)e, "bff_render_mesh_depth_u16: memset: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail((int)e, "%s: memset: %s", what, hipGetErrorString(e));
     CameraK K;
     for (int i = 0; i < 9; ++i) K.k[i] = cam_intr_host[i];
     const int64_t gx = ceil_div(n_faces, kRmBlock);                  // < 2^23
@@ -336,9 +496,36 @@ extern "C" int bff_render_mesh_depth_u16(const double *vertices, int64_t n_verti
         fpb = fpb < 1 ? 1 : (fpb > 8 ? 8 : fpb);
     }
     dim3 grid((unsigned)gx, (unsigned)ceil_div(n_frames, fpb));
-    render_mesh_depth_kernel<<<grid, kRmBlock, 0, st>>>(vertices, n_vertices, nv_pad, faces, n_faces, inv_pose, K, n_frames,
-                                                        fpb, height, width, depth_h, depth_w, scratch_u32);
-    int rc = launched("bff_render_mesh_depth_u16");
+    if (clip)
+        render_mesh_depth_clip_kernel<<<grid, kRmBlock, 0, st>>>(vertices, n_vertices, nv_pad, faces, n_faces, inv_pose, K,
+                                                                 n_frames, fpb, height, width, depth_h, depth_w, near_clip,
+                                                                 scratch_u32);
+    else
+        render_mesh_depth_kernel<<<grid, kRmBlock, 0, st>>>(vertices, n_vertices, nv_pad, faces, n_faces, inv_pose, K, n_frames,
+                                                            fpb, height, width, depth_h, depth_w, scratch_u32);
+    int rc = launched(what);
     if (rc != BFF_OK) return rc;
-    return narrow_frames(scratch_u32, total, out_u16, st, "bff_render_mesh_depth_u16");
+    return narrow_frames(scratch_u32, total, out_u16, st, what);
+}
+
+extern "C" int bff_render_mesh_depth_u16(const double *vertices, int64_t n_vertices, int64_t nv_pad, const int32_t *faces,
+                                         int64_t n_faces, const double *inv_pose, const double *cam_intr_host,
+                                         int32_t n_frames, int32_t height, int32_t width, int32_t depth_h, int32_t depth_w,
+                                         int32_t frames_per_block, uint32_t *scratch_u32, uint16_t *out_u16, void *stream)
+{
+    return render_mesh("bff_render_mesh_depth_u16", false, 0.0, vertices, n_vertices, nv_pad, faces, n_faces, inv_pose,
+                       cam_intr_host, n_frames, height, width, depth_h, depth_w, frames_per_block, scratch_u32, out_u16, stream);
+}
+
+extern "C" int bff_render_mesh_depth_clip_u16(const double *vertices, int64_t n_vertices, int64_t nv_pad, const int32_t *faces,
+                                              int64_t n_faces, const double *inv_pose, const double *cam_intr_host,
+                                              int32_t n_frames, int32_t height, int32_t width, int32_t depth_h,
+                                              int32_t depth_w, double near_clip, int32_t frames_per_block,
+                                              uint32_t *scratch_u32, uint16_t *out_u16, void *stream)
+{
+    // the comparisons fail on NaN
+    BFF_REQUIRE(near_clip > 0.0 && near_clip < 65.535, "bff_render_mesh_depth_clip_u16: near_clip must lie in (0, 65.535) metres");
+    return render_mesh("bff_render_mesh_depth_clip_u16", true, near_clip, vertices, n_vertices, nv_pad, faces, n_faces,
+                       inv_pose, cam_intr_host, n_frames, height, width, depth_h, depth_w, frames_per_block, scratch_u32,
+                       out_u16, stream);
 }

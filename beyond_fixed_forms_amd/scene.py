@@ -398,6 +398,24 @@ def rendered_depth_stride(cfg) -> int:
     return cloud or mesh
 
 
+MESH_NEAR_CLIP_LIMIT = 65.535      # metres: the largest depth a uint16 millimetre frame holds
+
+
+def mesh_near_clip(cfg) -> float:
+    """The optional config key `mesh_near_clip`, in metres: 0 (absent, None) = a triangle of the mesh that reaches behind
+    the camera plane is dropped whole; a value in (0, 65.535) = it is clipped at that depth instead
+    (bff_render_mesh_depth_clip_u16).  It belongs to depth_from_mesh: a positive value without that key is an error."""
+    v = cfg.get("mesh_near_clip", 0.0)
+    if v is None:
+        return 0.0
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+            not (0 <= v < MESH_NEAR_CLIP_LIMIT):                                        # NaN fails the comparison
+        raise ValueError(f"mesh_near_clip: 0 (off) or a depth in metres below {MESH_NEAR_CLIP_LIMIT} expected, got {v!r}")
+    if v > 0 and not depth_from_mesh_stride(cfg):
+        raise ValueError("mesh_near_clip is set but depth_from_mesh is not: only the mesh renderer clips")
+    return float(v)
+
+
 def rendered_depth_size(h, w, stride):
     return -(-h // stride), -(-w // stride)
 
@@ -451,13 +469,13 @@ def mesh_for_render(faces, xyz, n_points, unsort=None, vertices=None, n_vertices
 
 
 def rendered_depth_on_device(xyz, n_points, inv_pose_host, cam_intr, h, w, stride, tile_bounds=None,
-                             raw_depth_resident=None, inv_pose_dev=None, mesh=None):
+                             raw_depth_resident=None, inv_pose_dev=None, mesh=None, near_clip=0.0):
     """host_depth_to_device for a scene without depth frames: one frame per row of inv_pose_host (the slots' inverse
     poses, f64 [slots][16]) rendered from the sorted cloud `xyz` on its device (bff_render_depth_u16, one call for all
     slots, on the current stream) at 1 / stride of the working resolution, handed to raw_depth_on_device like the PNGs'
     uint16 frames -> (depth, depth_raw, depth_size).  inv_pose_dev: the same poses already on the device (ingest.py
     sends them through its pinned staging).  mesh (mesh_for_render's triple): the frames are rasterised from these
-    triangles instead (bff_render_mesh_depth_u16)."""
+    triangles instead (bff_render_mesh_depth_u16), clipped at near_clip metres when that is positive (mesh_near_clip)."""
     from . import _lib
     dev = xyz.device
     if dev.type != "cuda":
@@ -469,7 +487,7 @@ def rendered_depth_on_device(xyz, n_points, inv_pose_host, cam_intr, h, w, strid
         torch.as_tensor(np.ascontiguousarray(inv_pose_host, dtype=np.float64).reshape(-1, 16)).to(dev)
     k33 = np.asarray(cam_intr, dtype=np.float64)[:3, :3]
     if mesh is not None:
-        raw = _lib.render_mesh_depth(mesh[0], mesh[1], mesh[2], inv, k33, h, w, dh, dw)
+        raw = _lib.render_mesh_depth(mesh[0], mesh[1], mesh[2], inv, k33, h, w, dh, dw, near_clip=near_clip)
     else:
         raw = _lib.render_depth(xyz, n_points, inv, k33, h, w, dh, dw, tile_bounds)
     return raw_depth_on_device(raw, n_points, h, w, raw_depth_resident)
@@ -544,6 +562,7 @@ def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -
     inv = np.stack([np.linalg.inv(np.asarray(scene.poses[f], dtype=np.float64)).reshape(16) for f in ids]) if ids \
         else np.zeros((0, 16))                                                      # :425
     stride = rendered_depth_stride(cfg)
+    near_clip = mesh_near_clip(cfg)
     mesh = checked_mesh(scene, n) if depth_from_mesh_stride(cfg) else None        # raises before anything is uploaded
     if not stride:
         depth3 = host_depth_to_device(scene, ids, n, h, w, dev, raw_depth_resident)
@@ -559,7 +578,8 @@ def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -
             faces, verts, nv = mesh
             mesh = mesh_for_render(torch.as_tensor(faces).to(dev), xyz, n, unsort,
                                    None if verts is None else torch.as_tensor(verts).to(dev), nv)
-        depth3 = rendered_depth_on_device(xyz, n, inv, scene.cam_intr, h, w, stride, bounds, raw_depth_resident, mesh=mesh)
+        depth3 = rendered_depth_on_device(xyz, n, inv, scene.cam_intr, h, w, stride, bounds, raw_depth_resident, mesh=mesh,
+                                          near_clip=near_clip)
     return new_geometry(scene, h, w, n, ids, inv, n_viewed, xyz, depth3, bounds, unsort, t32(perm))
 
 

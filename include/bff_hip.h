@@ -32,7 +32,7 @@ extern "C" {
 #define BFF_E_ARG (-1)      /* null pointer / negative size / unsupported parameter */
 #define BFF_E_LIMIT (-2)    /* size beyond what a kernel supports (documented per call) */
 
-#define BFF_ABI_VERSION 12
+#define BFF_ABI_VERSION 13
 
 int bff_abi_version(void);
 const char *bff_last_error(void);
@@ -236,7 +236,8 @@ int bff_render_depth_u16(const double *xyz, int64_t n_points, int64_t n_pad, con
  *     px = ((K00 * c_0 + K01 * c_1) + K02 * c_2) / c_2,  py = ((K10 * c_0 + K11 * c_1) + K12 * c_2) / c_2
  *   (plain products and sums, no fma), and r = 1.0 / c_2.
  * Triangle in frame f:  takes part iff all three vertices have c_2 > 0, |px| < 2^24 and |py| < 2^24 (comparisons on the
- *   doubles: NaN fails).  A triangle that crosses the camera plane is therefore dropped, not clipped.
+ *   doubles: NaN fails).  A triangle that crosses the camera plane is therefore dropped, not clipped
+ *   (bff_render_mesh_depth_clip_u16 clips it at a near plane instead).
  * Sample point of texel (i, j):  X = (j + 0.5) * (width / depth_w) - 0.5,  Y = (i + 0.5) * (height / depth_h) - 0.5
  *   (the quotients in float64): the pixel position the bilinear resize maps to the centre of that texel.
  * Coverage, with (x_k, y_k) = (px, py) of the triangle's vertex k:
@@ -257,6 +258,39 @@ int bff_render_mesh_depth_u16(const double *vertices, int64_t n_vertices, int64_
                               int64_t n_faces, const double *inv_pose, const double *cam_intr_host, int32_t n_frames,
                               int32_t height, int32_t width, int32_t depth_h, int32_t depth_w, int32_t frames_per_block,
                               uint32_t *scratch_u32, uint16_t *out_u16, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * bff_render_mesh_depth_u16 with the triangles clipped at a near plane instead of dropped when they reach behind the
+ * camera: a closed room seen from inside has depth in every texel.  Everything not named here is exactly
+ * bff_render_mesh_depth_u16's definition (sample points, coverage test, S, perspective-correct z, m = rint(z * 1000.0),
+ * 1 <= m <= 65535, minimum per texel, 0 if none; every operation one IEEE float64 operation in the order written, without
+ * contraction), and so are the other arguments, the limits and the early returns.
+ *   near_clip  zn, metres: a finite double with 0 < zn < 65.535 (anything else, NaN included, is BFF_E_ARG)
+ * Per triangle and frame:
+ *   Camera points  c_k = (c_0, c_1, c_2) of the three vertices by the fma chains, as above.  The triangle takes part only
+ *     if all nine values are finite.
+ *   Inside test    vertex k is inside iff its c_2 >= zn.
+ *   Polygon        walk the edges k -> (k + 1) mod 3 for k = 0, 1, 2: if k is inside, emit vertex k; if k and k + 1 lie on
+ *     different sides, emit the intersection.  The result has 0, 3 or 4 vertices.
+ *   Intersection   always computed from the inside vertex p towards the outside vertex q, whichever way the edge is
+ *     walked:  t = (p_2 - zn) / (p_2 - q_2),  I_0 = p_0 + t * (q_0 - p_0),  I_1 = p_1 + t * (q_1 - p_1),  I_2 = zn exactly.
+ *     Two triangles that share a straddling edge therefore get bit-identical cut points: no crack opens between them.
+ *   Screen position  an original vertex has its px, py and r = 1.0 / c_2 as above; a cut point has
+ *     px = ((K00 * I_0 + K01 * I_1) + K02 * zn) / zn,  py likewise with K's second row,  r = 1.0 / zn.
+ *   Fan            the polygon (v0, v1, ...) in emission order is drawn as (v0, v1, v2) and, with four vertices, also
+ *     (v0, v2, v3).  Each is a triangle of the definition above: dropped if one of its three vertices fails |px| < 2^24,
+ *     |py| < 2^24; S = 0 where two of its vertices coincide; the texel-box argument is the same.
+ * Consequences:
+ *   a triangle wholly nearer than zn is dropped;
+ *   a triangle wholly at or beyond zn is drawn with exactly bff_render_mesh_depth_u16's arithmetic, so a mesh that never
+ *     comes nearer than zn gives the same bytes as bff_render_mesh_depth_u16;
+ *   a vertex with c_2 == zn gives t = 0, hence a fan triangle with two vertices at one position, which draws nothing;
+ *   the result is still a minimum of integers: the same bytes on every run, independent of face order and frame tile.
+ * zn bounds the nearest depth a frame can hold (rint(zn * 1000) mm); which value serves a dataset best is untuned. */
+int bff_render_mesh_depth_clip_u16(const double *vertices, int64_t n_vertices, int64_t nv_pad, const int32_t *faces,
+                                   int64_t n_faces, const double *inv_pose, const double *cam_intr_host, int32_t n_frames,
+                                   int32_t height, int32_t width, int32_t depth_h, int32_t depth_w, double near_clip,
+                                   int32_t frames_per_block, uint32_t *scratch_u32, uint16_t *out_u16, void *stream);
 
 /* Texels of a triangle's clipped texel box up to which the triangle's own lane walks the box; a larger box is walked
  * by the whole wave.  The box of a triangle along one axis: the texels t with floor((lo + 0.5) / s - 0.5) - 1 <= t <=
