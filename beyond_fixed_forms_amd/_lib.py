@@ -33,6 +33,7 @@ SIGNATURES = {
     "bff_point_tile_bounds": [_P, _L, _L, _P, _P],
     "bff_count_viewed": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _I, _P, _P, _P],
     "bff_render_depth_u16": [_P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "bff_render_splat_depth_u16": [_P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _D, _I, _P, _P, _P, _P],
     "bff_render_mesh_depth_u16": [_P, _L, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "bff_render_mesh_depth_clip_u16": [_P, _L, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _D, _I, _P, _P, _P],
     "bff_popcount_rows": [_P, _P, _I, _L, _P, _P],
@@ -83,14 +84,14 @@ SIGNATURES = {
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
          "bff_masks2d_tile_pixels": (c_int32, []), "bff_mask_lookup_rows": (c_int32, [c_int32, c_int32, c_int64]),
          "bff_chunk_mask_words": (c_int32, [c_int64]), "bff_label_plane_stride": (c_int64, [c_int64]), "bff_resolve_overlaps_max_rows": (c_int32, []),
-         "bff_point_tile_size": (c_int32, []), "bff_mesh_lane_box": (c_int32, []), "bff_depth_tiled_texels": (c_int64, [c_int32, c_int32]), "bff_merge_scratch_words": (c_int64, [c_int32]), "bff_merge_uses_chunk_bound": (c_int32, [c_int64]),
+         "bff_point_tile_size": (c_int32, []), "bff_mesh_lane_box": (c_int32, []), "bff_splat_lane_box": (c_int32, []), "bff_depth_tiled_texels": (c_int64, [c_int32, c_int32]), "bff_merge_scratch_words": (c_int64, [c_int32]), "bff_merge_uses_chunk_bound": (c_int32, [c_int64]),
          "bff_profile_next_merge": (c_int32, [_P, _P]), "bff_group_slice_cap": (c_int32, [c_int32, c_int32]),
          "bff_point_threshold_scratch_words": (c_int64, [c_int64]), "bff_point_threshold_capacity": (c_int32, []), "bff_point_threshold_capacity_set": (c_int32, [c_int32]), "bff_scene_header_words": (c_int32, [c_int32, c_int32]), "bff_scene_struct_bytes": (c_int32, [c_int32]),
          "bff_host_component_csr": (c_int32, [_P, _P, _I, _I, _P, _P, _P, _P]),
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class BffLibraryError(RuntimeError):
@@ -367,14 +368,18 @@ RENDER_SCRATCH_TEXELS = 1 << 26     # texels of the renderer's uint32 scratch (2
 
 
 def render_depth(xyz_soa, n_points, inv_pose, cam_intr, height, width, depth_h, depth_w, tile_bounds=None,
-                 frames_per_block=0, scratch_texels=None):
+                 frames_per_block=0, scratch_texels=None, splat_radius=0.0):
     """Depth frames out of the cloud itself (bff_render_depth_u16): every point of `xyz_soa` that projects in bounds and
     in front of the camera of frame f (inv_pose f64 [F][16], device) splats rint(z * 1000) into texel (v * depth_h //
     height, u * depth_w // width) of frame f, a texel keeps the minimum, 0 = no point.  -> int16 [F][depth_h][depth_w] (the
     uint16 millimetres, as the decoded depth PNGs are held), on the current launch stream.  The call needs a uint32
     scratch texel per result texel: at most scratch_texels (default RENDER_SCRATCH_TEXELS) are allocated, and the frames
     are rendered in runs of as many as fit (each run reads the cloud once more).  frames_per_block: the kernel's frame
-    tile, 0 = the library's choice."""
+    tile, 0 = the library's choice.  splat_radius: 0 = one texel per point as above; a positive radius in metres = every
+    point also covers the texels whose sample point lies within its footprint (bff_render_splat_depth_u16, the
+    definition is the header's; anything else is rejected by the library)."""
+    splat_radius = float(splat_radius)
+    splat = splat_radius != 0.0                                # NaN included: the library rejects it
     k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
     f, plane = int(inv_pose.shape[0]), int(depth_h) * int(depth_w)
     out = torch.empty((f, int(depth_h), int(depth_w)), dtype=torch.int16, device=xyz_soa.device)
@@ -382,9 +387,13 @@ def render_depth(xyz_soa, n_points, inv_pose, cam_intr, height, width, depth_h, 
     scratch = torch.empty(max(per * plane, 1), dtype=i32, device=xyz_soa.device)
     for f0 in range(0, max(f, 1), per):
         f1 = min(f, f0 + per)
-        call("bff_render_depth_u16", _ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(inv_pose[f0:f1], f64),
-             ctypes.cast(k, c_void_p), f1 - f0, int(height), int(width), int(depth_h), int(depth_w), int(frames_per_block),
-             _ptr(scratch), _ptr(out[f0:f1]), _ptr(tile_bounds, f64))
+        head = (_ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(inv_pose[f0:f1], f64), ctypes.cast(k, c_void_p), f1 - f0,
+                int(height), int(width), int(depth_h), int(depth_w))
+        tail = (int(frames_per_block), _ptr(scratch), _ptr(out[f0:f1]), _ptr(tile_bounds, f64))
+        if splat:
+            call("bff_render_splat_depth_u16", *head, splat_radius, *tail)
+        else:
+            call("bff_render_depth_u16", *head, *tail)
     return out
 
 

@@ -28,6 +28,10 @@ DEFAULTS = dict(
     # behind the camera) is clipped at this depth instead of dropped whole (scene.mesh_near_clip); 0 = off, the frames as
     # they were.  0.05 is a starting value nobody has tuned
     mesh_near_clip=0.0,
+    # not a key of the reference either: metres.  With depth_from_cloud on, every point of the cloud covers the texels within
+    # a camera-facing square of this half-width instead of one texel (scene.cloud_splat_radius): near surfaces close their
+    # own gaps.  0 = off, the frames as they were.  About the cloud's point spacing; no value has been tuned
+    cloud_splat_radius=0.0,
 )
 
 

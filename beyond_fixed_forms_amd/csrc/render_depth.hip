@@ -13,7 +13,7 @@
 // across the frames of the block's frame tile, poses wave-uniform, the tile culled against tile_bounds in groups of 8
 // frames.  A minimum of integers does not depend on the order of its operands: the frames are the same bytes on every run.
 // Further down: the same frames rasterised from a triangle mesh (bff_render_mesh_depth_u16), through the same scratch and
-// the same narrowing kernel.
+// the same narrowing kernel; after it the point z-buffer with a footprint per point (bff_render_splat_depth_u16).
 #include "geom.h"
 
 namespace bff {
@@ -399,6 +399,102 @@ __global__ __launch_bounds__(kRmBlock) void render_mesh_depth_clip_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The point z-buffer with a surfel footprint per point (bff_render_splat_depth_u16): render_depth_kernel's shape (1024
+// sorted points per block, 4 per thread in registers across the block's frame tile, poses wave-uniform, the tile culled
+// in groups of 8 frames), a sibling with its own lines.  Per frame and point: the own-texel atomicMin as there, then the
+// texels whose sample point lies within (Rx, Ry) pixels of the point's integer pixel -- a rectangle of the frame, found
+// per axis (splat_range) and then walked without any further test.  A rectangle of at most kRsLaneBox texels is walked
+// by the lane that owns the point; a larger one (a point near the camera can cover the frame) by the whole wave, as in
+// the mesh kernel: ballot, broadcast of m and the rectangle, 64 lanes stride over it.
+constexpr int kRsLaneBox = 64;                                     // texels a lane walks alone; beyond: the wave path
+
+// Texels t of one axis with fabs(X_t - c) <= R, X_t = (t + 0.5) * s - 0.5 (the header's comparison, operation by
+// operation), clipped to [0, n): -> first, last (first > last = none).  X_t ascends with t and so does the rounded
+// difference, so the texels that pass are a run; texel_range gives a run that holds it (one texel wider at either end
+// than [c - R, c + R] reaches: far more than the roundings here move), and both ends come in until they pass.
+__device__ __forceinline__ void splat_range(double c, double R, double s, int n, int &first, int &last)
+{
+    texel_range(__dsub_rn(c, R), __dadd_rn(c, R), s, n, first, last);
+    auto passes = [&](int t) { return fabs(__dsub_rn(__dsub_rn(__dmul_rn((double)t + 0.5, s), 0.5), c)) <= R; };
+    while (first <= last && !passes(first)) ++first;
+    while (last >= first && !passes(last)) --last;
+}
+
+__global__ __launch_bounds__(kRdBlock) void render_splat_depth_kernel(
+    const double *__restrict__ xyz, int64_t n_points, int64_t n_pad, const double *__restrict__ inv_pose, CameraK K,
+    int n_frames, int frames_per_block, int H, int W, int dh, int dw, double radius, uint32_t *__restrict__ scratch,
+    const double *__restrict__ tile_bounds)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t word0 = (int64_t)blockIdx.x * kRdWordsPerBlock + (int64_t)wave * kRdPPT;     // the wave's first 64 points
+    const int f0 = blockIdx.y * frames_per_block;
+    const int f1 = min(n_frames, f0 + frames_per_block);
+    const int64_t plane = (int64_t)dh * dw;
+    const double dW = (double)W, dH = (double)H;
+    const double sx = dW / (double)dw, sy = dH / (double)dh;
+    const double krx = __dmul_rn(K.k[0], radius), kry = __dmul_rn(K.k[4], radius);
+
+    double px[kRdPPT], py[kRdPPT], pz[kRdPPT];
+    bool valid[kRdPPT];
+#pragma unroll
+    for (int j = 0; j < kRdPPT; ++j) {
+        const int64_t n = (word0 + j) * kWave + lane;
+        valid[j] = n < n_points;                                   // padding lanes take no part (they read point 0)
+        const int64_t m = valid[j] ? n : 0;
+        px[j] = xyz[m];
+        py[j] = xyz[n_pad + m];
+        pz[j] = xyz[2 * n_pad + m];
+    }
+
+    for (int g0 = f0; g0 < f1; g0 += kRdCullGroup) {
+        const int g1 = min(f1, g0 + kRdCullGroup);
+        uint64_t culled = 0;
+        if (tile_bounds && word0 * kWave < n_points)               // wave-uniform; only in-bounds points take part, so
+            culled = cull_frames(tile_bounds + 6 * (word0 / kRdPPT), inv_pose, K, g0, g1, lane, dW, dH);   // culling stays exact
+        for (int f = g0; f < g1; ++f) {
+            if ((culled >> (8 * (f - g0))) & 1) continue;          // wave-uniform
+            const double *P = inv_pose + 16 * (int64_t)f;
+            uint32_t *img = scratch + (int64_t)f * plane;
+#pragma unroll
+            for (int j = 0; j < kRdPPT; ++j) {
+                double cz, u, v;
+                camera_pixel(P, K, px[j], py[j], pz[j], cz, u, v);
+                const double m = rint(__dmul_rn(cz, 1000.0));
+                const bool splat = valid[j] && pixel_in_bounds(u, v, dW, dH) && (cz > 0.0) && (m >= 1.0) && (m <= 65535.0);
+                const uint32_t mm = splat ? (uint32_t)m : kRdEmpty;
+                TexelBox b = {0, 0, 0, 0};
+                if (splat) {
+                    // own texel, as render_depth_kernel: u < W and v < H, so tx < dw and ty < dh
+                    atomicMin(img + ((int)(((unsigned)(int)v * (unsigned)dh) / (unsigned)H) * dw +
+                                     (int)(((unsigned)(int)u * (unsigned)dw) / (unsigned)W)), mm);
+                    int j1, i1;
+                    splat_range(u, krx / cz, sx, dw, b.j0, j1);
+                    splat_range(v, kry / cz, sy, dh, b.i0, i1);
+                    if (j1 >= b.j0 && i1 >= b.i0) {
+                        b.bw = j1 - b.j0 + 1;
+                        b.count = b.bw * (i1 - b.i0 + 1);          // <= dh * dw < 2^31
+                    }
+                }
+                if (b.count > 0 && b.count <= kRsLaneBox)          // the lane's own walk, row by row
+                    for (int k = 0, i = b.i0, t = b.j0; k < b.count; ++k) {
+                        atomicMin(img + (i * dw + t), mm);         // result unused: returnless
+                        if (++t == b.j0 + b.bw) t = b.j0, ++i;
+                    }
+                uint64_t big = __ballot(b.count > kRsLaneBox);     // every lane of the wave is here: no early exit above
+                while (big) {
+                    const int src = __ffsll((unsigned long long)big) - 1;
+                    big &= big - 1;
+                    const uint32_t wm = __shfl(mm, src);
+                    const int wj0 = __shfl(b.j0, src), wi0 = __shfl(b.i0, src), wbw = __shfl(b.bw, src), wcount = __shfl(b.count, src);
+                    for (unsigned k = lane; k < (unsigned)wcount; k += kWave)       // unsigned: wcount + 63 may pass 2^31
+                        atomicMin(img + ((wi0 + (int)(k / (unsigned)wbw)) * dw + wj0 + (int)(k % (unsigned)wbw)), wm);
+                }
+            }
+        }
+    }
+}
+
 // the scratch of a render call -> its uint16 frames
 static int narrow_frames(const uint32_t *scratch_u32, int64_t total, uint16_t *out_u16, hipStream_t st, const char *what)
 {
@@ -412,50 +508,79 @@ static int narrow_frames(const uint32_t *scratch_u32, int64_t total, uint16_t *o
 
 using namespace bff;
 
-extern "C" int bff_render_depth_u16(const double *xyz, int64_t n_points, int64_t n_pad, const double *inv_pose,
-                                    const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width,
-                                    int32_t depth_h, int32_t depth_w, int32_t frames_per_block, uint32_t *scratch_u32,
-                                    uint16_t *out_u16, const double *tile_bounds, void *stream)
+// both point entry points: the checks, the early returns, the fill of the scratch, one of the two kernels, the narrowing
+static int render_points(const char *what, bool splat, double splat_radius, const double *xyz, int64_t n_points, int64_t n_pad,
+                         const double *inv_pose, const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width,
+                         int32_t depth_h, int32_t depth_w, int32_t frames_per_block, uint32_t *scratch_u32, uint16_t *out_u16,
+                         const double *tile_bounds, void *stream)
 {
-    BFF_REQUIRE(n_points >= 0 && n_pad >= n_points && n_frames >= 0 && frames_per_block >= 0, "bff_render_depth_u16: bad sizes");
-    BFF_REQUIRE(height > 0 && width > 0 && depth_h > 0 && depth_w > 0, "bff_render_depth_u16: bad image size");
-    BFF_LIMIT((int64_t)height * width < (1ll << 31), "bff_render_depth_u16: image larger than 2^31 pixels");
-    BFF_LIMIT((int64_t)depth_h * depth_w < (1ll << 31), "bff_render_depth_u16: depth frame larger than 2^31 texels");
+    BFF_REQUIRE(n_points >= 0 && n_pad >= n_points && n_frames >= 0 && frames_per_block >= 0, "%s: bad sizes", what);
+    BFF_REQUIRE(height > 0 && width > 0 && depth_h > 0 && depth_w > 0, "%s: bad image size", what);
+    BFF_LIMIT((int64_t)height * width < (1ll << 31), "%s: image larger than 2^31 pixels", what);
+    BFF_LIMIT((int64_t)depth_h * depth_w < (1ll << 31), "%s: depth frame larger than 2^31 texels", what);
     BFF_LIMIT((int64_t)height * depth_h < (1ll << 31) && (int64_t)width * depth_w < (1ll << 31),
-              "bff_render_depth_u16: pixel x texel products beyond 2^31 (height * depth_h, width * depth_w)");
-    BFF_LIMIT(n_frames <= 65535, "bff_render_depth_u16: too many frames");
+              "%s: pixel x texel products beyond 2^31 (height * depth_h, width * depth_w)", what);
+    BFF_LIMIT(n_frames <= 65535, "%s: too many frames", what);
     const int64_t gx = ceil_div(n_points, kRdPtsPerBlock);
     const int64_t n_narrow = ceil_div(ceil_div((int64_t)n_frames * depth_h * depth_w, 4), 256);
-    BFF_LIMIT(gx < (1ll << 31) && n_narrow < (1ll << 31), "bff_render_depth_u16: too many points / texels for one launch");
+    BFF_LIMIT(gx < (1ll << 31) && n_narrow < (1ll << 31), "%s: too many points / texels for one launch", what);
+    // the comparisons fail on NaN; checked before the early returns, as the sizes are (K: where the caller gave one)
+    BFF_REQUIRE(!splat || (splat_radius > 0.0 && std::isfinite(splat_radius)), "%s: splat_radius must be finite and > 0", what);
+    BFF_REQUIRE(!splat || !cam_intr_host || (cam_intr_host[0] > 0.0 && std::isfinite(cam_intr_host[0]) && cam_intr_host[4] > 0.0 &&
+                                             std::isfinite(cam_intr_host[4])), "%s: K00 and K11 must be finite and > 0", what);
     if (n_frames == 0) return BFF_OK;
-    BFF_REQUIRE(out_u16, "bff_render_depth_u16: null pointer");
+    BFF_REQUIRE(out_u16, "%s: null pointer", what);
     hipStream_t st = as_stream(stream);
     const int64_t total = (int64_t)n_frames * depth_h * depth_w;
     if (n_points == 0) {                                             // nothing splats: every texel is "no depth"
         hipError_t e = hipMemsetAsync(out_u16, 0, sizeof(uint16_t) * (size_t)total, st);
-        if (e != hipSuccess) return fail((int)e, "bff_render_depth_u16: memset: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail((int)e, "%s: memset: %s", what, hipGetErrorString(e));
         return BFF_OK;
     }
-    BFF_REQUIRE(xyz && inv_pose && cam_intr_host && scratch_u32, "bff_render_depth_u16: null pointer");
+    BFF_REQUIRE(xyz && inv_pose && cam_intr_host && scratch_u32, "%s: null pointer", what);
     hipError_t e = hipMemsetAsync(scratch_u32, 0xff, sizeof(uint32_t) * (size_t)total, st);
-    if (e != hipSuccess) return fail((int)e, "bff_render_depth_u16: memset: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail((int)e, "%s: memset: %s", what, hipGetErrorString(e));
     CameraK K;
     for (int i = 0; i < 9; ++i) K.k[i] = cam_intr_host[i];
     // the culling table's tiles are the sweep's (bff_point_tile_bounds): they must be this kernel's waves
-    BFF_REQUIRE(!tile_bounds || bff_point_tile_size() == kRdPPT * kWave, "bff_render_depth_u16: tile_bounds holds tiles of %d "
-                "points, the renderer's waves own %d", bff_point_tile_size(), kRdPPT * kWave);
+    BFF_REQUIRE(!tile_bounds || bff_point_tile_size() == kRdPPT * kWave, "%s: tile_bounds holds tiles of %d points, the "
+                "renderer's waves own %d", what, bff_point_tile_size(), kRdPPT * kWave);
     int fpb = frames_per_block;
     if (fpb == 0) {                                                  // >= ~4096 blocks in flight, tiles of up to 8 frames
         fpb = (int)((int64_t)n_frames * gx / 4096);
         fpb = fpb < 1 ? 1 : (fpb > kRdCullGroup ? kRdCullGroup : fpb);
     }
     dim3 grid((unsigned)gx, (unsigned)ceil_div(n_frames, fpb));
-    render_depth_kernel<<<grid, kRdBlock, 0, st>>>(xyz, n_points, n_pad, inv_pose, K, n_frames, fpb, height, width, depth_h,
-                                                   depth_w, scratch_u32, tile_bounds);
-    int rc = launched("bff_render_depth_u16");
+    if (splat)
+        render_splat_depth_kernel<<<grid, kRdBlock, 0, st>>>(xyz, n_points, n_pad, inv_pose, K, n_frames, fpb, height, width,
+                                                             depth_h, depth_w, splat_radius, scratch_u32, tile_bounds);
+    else
+        render_depth_kernel<<<grid, kRdBlock, 0, st>>>(xyz, n_points, n_pad, inv_pose, K, n_frames, fpb, height, width, depth_h,
+                                                       depth_w, scratch_u32, tile_bounds);
+    int rc = launched(what);
     if (rc != BFF_OK) return rc;
-    return narrow_frames(scratch_u32, total, out_u16, st, "bff_render_depth_u16");
+    return narrow_frames(scratch_u32, total, out_u16, st, what);
 }
+
+extern "C" int bff_render_depth_u16(const double *xyz, int64_t n_points, int64_t n_pad, const double *inv_pose,
+                                    const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width,
+                                    int32_t depth_h, int32_t depth_w, int32_t frames_per_block, uint32_t *scratch_u32,
+                                    uint16_t *out_u16, const double *tile_bounds, void *stream)
+{
+    return render_points("bff_render_depth_u16", false, 0.0, xyz, n_points, n_pad, inv_pose, cam_intr_host, n_frames, height,
+                         width, depth_h, depth_w, frames_per_block, scratch_u32, out_u16, tile_bounds, stream);
+}
+
+extern "C" int bff_render_splat_depth_u16(const double *xyz, int64_t n_points, int64_t n_pad, const double *inv_pose,
+                                          const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width,
+                                          int32_t depth_h, int32_t depth_w, double splat_radius, int32_t frames_per_block,
+                                          uint32_t *scratch_u32, uint16_t *out_u16, const double *tile_bounds, void *stream)
+{
+    return render_points("bff_render_splat_depth_u16", true, splat_radius, xyz, n_points, n_pad, inv_pose, cam_intr_host,
+                         n_frames, height, width, depth_h, depth_w, frames_per_block, scratch_u32, out_u16, tile_bounds, stream);
+}
+
+extern "C" int bff_splat_lane_box(void) { return kRsLaneBox; }
 
 extern "C" int bff_mesh_lane_box(void) { return kRmLaneBox; }
 

@@ -30,11 +30,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .scene import (DeviceScene, SceneGeometry, checked_mesh, class_inv_poses, class_word_bits, concat_confidences,
-                    confidence_dtype, count_geometry_viewed, depth_from_mesh_stride, device_scene, frame_table, frame_union,
-                    label_ids, masks_all_rle, mesh_for_render, mesh_near_clip, new_geometry, padded_points, prepare_class,
-                    prepare_geometry, prepare_scene, raw_depth_on_device, rendered_depth_on_device, rendered_depth_stride,
-                    run_tables, slots_on_first_use, viewed_frame_ids, with_viewed_counts)
+from .scene import (DeviceScene, SceneGeometry, checked_mesh, class_inv_poses, class_word_bits, cloud_splat_radius,
+                    concat_confidences, confidence_dtype, count_geometry_viewed, depth_from_mesh_stride, device_scene,
+                    frame_table, frame_union, label_ids, masks_all_rle, mesh_for_render, mesh_near_clip, new_geometry,
+                    padded_points, prepare_class, prepare_geometry, prepare_scene, raw_depth_on_device,
+                    rendered_depth_on_device, rendered_depth_stride, run_tables, slots_on_first_use, viewed_frame_ids,
+                    with_viewed_counts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libbff_host.so")
@@ -196,6 +197,7 @@ def _geometry_to_device(scene, cfg, ids, n_viewed, dev, staging, n_threads, lap=
     lap("pose inverses")
     stride = rendered_depth_stride(cfg)
     near_clip = mesh_near_clip(cfg)                  # raises before any upload, like the two-keys error above
+    splat_radius = cloud_splat_radius(cfg)           # likewise
     if stride:                                       # no depth frames: rendered from the cloud, so the cloud goes first
         mesh = checked_mesh(scene, pts.shape[0]) if depth_from_mesh_stride(cfg) else None    # raises before any upload
         xyz, unsort, perm, bounds = _cloud_to_device(pts, dev, staging)
@@ -203,7 +205,7 @@ def _geometry_to_device(scene, cfg, ids, n_viewed, dev, staging, n_threads, lap=
         if mesh is not None:
             mesh = _mesh_to_device(mesh, xyz, pts.shape[0], unsort, dev, staging)
         depth3 = _depth_to_device(scene, ids, pts.shape[0], h, w, dev, staging, n_threads,
-                                  cloud=(xyz, inv, scene.cam_intr, stride, bounds, mesh, near_clip))
+                                  cloud=(xyz, inv, scene.cam_intr, stride, bounds, mesh, near_clip, splat_radius))
         lap("depth (rendered from the cloud / the mesh)")
         return new_geometry(scene, h, w, pts.shape[0], ids, inv, n_viewed, xyz, depth3, bounds, unsort, perm)
     depth3 = _depth_to_device(scene, ids, pts.shape[0], h, w, dev, staging, n_threads)
@@ -260,19 +262,19 @@ def _depth_to_device(scene, depth_ids, n, h, w, dev, staging, n_threads, cloud=N
     """The frames `depth_ids` of a scene on the device, in that order (scene.host_depth_to_device's layout rules): packed
     into pinned staging by native threads and uploaded as ONE asynchronous copy.  -> (depth, depth_raw, depth_size), or
     None when the frames are of mixed sizes / dtypes (the caller takes the exact slow path).
-    cloud = (xyz, the frames' inverse poses on the host, K, stride, tile bounds, mesh, mesh_near_clip): the scene has no depth frames (config
-    key depth_from_cloud or depth_from_mesh); they are rendered from the cloud already laid out on the device, or from
+    cloud = (xyz, the frames' inverse poses on the host, K, stride, tile bounds, mesh, mesh_near_clip, cloud_splat_radius):
+    the scene has no depth frames (config key depth_from_cloud or depth_from_mesh); they are rendered from the cloud already laid out on the device, or from
     the mesh on the device (_mesh_to_device; None: from the cloud), on the current stream
     (scene.rendered_depth_on_device) -- no depth staging is taken and nothing crosses the bus but the poses."""
     if cloud is not None:
-        xyz, inv, cam_intr, stride, bounds, mesh, near_clip = cloud
+        xyz, inv, cam_intr, stride, bounds, mesh, near_clip, splat_radius = cloud
         inv_dev = None
         if inv.size:
             pstage = staging.get("render.poses", inv.nbytes)
             pstage.numpy()[:inv.nbytes].view(np.float64)[:] = inv.reshape(-1)
             inv_dev = pstage[:inv.nbytes].view(torch.float64).view(-1, 16).to(dev, non_blocking=True)
         return rendered_depth_on_device(xyz, n, inv, cam_intr, h, w, stride, bounds, inv_pose_dev=inv_dev, mesh=mesh,
-                                        near_clip=near_clip)
+                                        near_clip=near_clip, splat_radius=splat_radius)
     raw_depth = getattr(scene, "depths_raw", None)
     src = raw_depth if raw_depth is not None else scene.depths
     frames = [src[f] for f in depth_ids]

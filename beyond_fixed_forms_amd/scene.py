@@ -416,6 +416,21 @@ def mesh_near_clip(cfg) -> float:
     return float(v)
 
 
+def cloud_splat_radius(cfg) -> float:
+    """The optional config key `cloud_splat_radius`, in metres: 0 (absent, None) = a point of the cloud writes one texel
+    of its rendered frame; a positive value = it covers the texels within a camera-facing square of that half-width
+    (bff_render_splat_depth_u16).  It belongs to depth_from_cloud: a positive value without that key is an error."""
+    v = cfg.get("cloud_splat_radius", 0.0)
+    if v is None:
+        return 0.0
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+            not (0 <= v < np.inf):                                                      # NaN fails the comparison
+        raise ValueError(f"cloud_splat_radius: 0 (off) or a finite radius in metres expected, got {v!r}")
+    if v > 0 and not depth_from_cloud_stride(cfg):
+        raise ValueError("cloud_splat_radius is set but depth_from_cloud is not: only the point renderer splats")
+    return float(v)
+
+
 def rendered_depth_size(h, w, stride):
     return -(-h // stride), -(-w // stride)
 
@@ -469,13 +484,15 @@ def mesh_for_render(faces, xyz, n_points, unsort=None, vertices=None, n_vertices
 
 
 def rendered_depth_on_device(xyz, n_points, inv_pose_host, cam_intr, h, w, stride, tile_bounds=None,
-                             raw_depth_resident=None, inv_pose_dev=None, mesh=None, near_clip=0.0):
+                             raw_depth_resident=None, inv_pose_dev=None, mesh=None, near_clip=0.0, splat_radius=0.0):
     """host_depth_to_device for a scene without depth frames: one frame per row of inv_pose_host (the slots' inverse
     poses, f64 [slots][16]) rendered from the sorted cloud `xyz` on its device (bff_render_depth_u16, one call for all
     slots, on the current stream) at 1 / stride of the working resolution, handed to raw_depth_on_device like the PNGs'
     uint16 frames -> (depth, depth_raw, depth_size).  inv_pose_dev: the same poses already on the device (ingest.py
     sends them through its pinned staging).  mesh (mesh_for_render's triple): the frames are rasterised from these
-    triangles instead (bff_render_mesh_depth_u16), clipped at near_clip metres when that is positive (mesh_near_clip)."""
+    triangles instead (bff_render_mesh_depth_u16), clipped at near_clip metres when that is positive (mesh_near_clip).
+    splat_radius: positive = the cloud's points cover a footprint of that radius in metres (cloud_splat_radius,
+    bff_render_splat_depth_u16)."""
     from . import _lib
     dev = xyz.device
     if dev.type != "cuda":
@@ -489,7 +506,8 @@ def rendered_depth_on_device(xyz, n_points, inv_pose_host, cam_intr, h, w, strid
     if mesh is not None:
         raw = _lib.render_mesh_depth(mesh[0], mesh[1], mesh[2], inv, k33, h, w, dh, dw, near_clip=near_clip)
     else:
-        raw = _lib.render_depth(xyz, n_points, inv, k33, h, w, dh, dw, tile_bounds)
+        splat = dict(splat_radius=splat_radius) if splat_radius else {}          # key off: the call as it always was
+        raw = _lib.render_depth(xyz, n_points, inv, k33, h, w, dh, dw, tile_bounds, **splat)
     return raw_depth_on_device(raw, n_points, h, w, raw_depth_resident)
 
 
@@ -563,6 +581,7 @@ def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -
         else np.zeros((0, 16))                                                      # :425
     stride = rendered_depth_stride(cfg)
     near_clip = mesh_near_clip(cfg)
+    splat_radius = cloud_splat_radius(cfg)
     mesh = checked_mesh(scene, n) if depth_from_mesh_stride(cfg) else None        # raises before anything is uploaded
     if not stride:
         depth3 = host_depth_to_device(scene, ids, n, h, w, dev, raw_depth_resident)
@@ -579,7 +598,7 @@ def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -
             mesh = mesh_for_render(torch.as_tensor(faces).to(dev), xyz, n, unsort,
                                    None if verts is None else torch.as_tensor(verts).to(dev), nv)
         depth3 = rendered_depth_on_device(xyz, n, inv, scene.cam_intr, h, w, stride, bounds, raw_depth_resident, mesh=mesh,
-                                          near_clip=near_clip)
+                                          near_clip=near_clip, splat_radius=splat_radius)
     return new_geometry(scene, h, w, n, ids, inv, n_viewed, xyz, depth3, bounds, unsort, t32(perm))
 
 

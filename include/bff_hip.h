@@ -32,7 +32,7 @@ extern "C" {
 #define BFF_E_ARG (-1)      /* null pointer / negative size / unsupported parameter */
 #define BFF_E_LIMIT (-2)    /* size beyond what a kernel supports (documented per call) */
 
-#define BFF_ABI_VERSION 13
+#define BFF_ABI_VERSION 14
 
 int bff_abi_version(void);
 const char *bff_last_error(void);
@@ -220,6 +220,44 @@ int bff_render_depth_u16(const double *xyz, int64_t n_points, int64_t n_pad, con
                          const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width,
                          int32_t depth_h, int32_t depth_w, int32_t frames_per_block, uint32_t *scratch_u32,
                          uint16_t *out_u16, const double *tile_bounds, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * bff_render_depth_u16 with a surfel footprint per point: every point is a camera-facing square of half-width
+ * splat_radius metres and is offered to every texel whose sample point its projection reaches, so a near surface closes
+ * its own gaps (a fine frame of bff_render_depth_u16 is mostly empty texels, through which the background shows) and a
+ * far one has depth in every texel.  Everything not named here -- the other arguments, out_u16, scratch_u32, the limits
+ * and the early returns -- is bff_render_depth_u16's.
+ *   splat_radius  r, metres: a finite double > 0 (anything else, NaN included, is BFF_E_ARG); K00 and K11 (cam_intr_host[0]
+ *                 and [4]) must be finite and > 0 (BFF_E_ARG)
+ * Every operation below is one IEEE float64 operation in the order written, without contraction.  For frame f and point
+ * n < n_points:
+ *   c, u, v and m = rint(c_2 * 1000.0) are exactly bff_render_depth_u16's (the sweep's fma chains, IEEE division, half to
+ *   even, bounds tested on the doubles);
+ *   the point takes part iff it would splat there: in bounds, c_2 > 0, 1 <= m <= 65535;
+ *   Own texel   as bff_render_depth_u16: texel ((v * depth_h) / height, (u * depth_w) / width) is offered m;
+ *   Footprint   radii in pixels:  Rx = (K00 * r) / c_2,  Ry = (K11 * r) / c_2.  Sample points of the texels are the mesh
+ *     renderer's:  X_j = (j + 0.5) * (width / depth_w) - 0.5,  Y_i = (i + 0.5) * (height / depth_h) - 0.5.  Texel (i, j) of
+ *     the frame is offered m iff fabs(X_j - u) <= Rx and fabs(Y_i - v) <= Ry.  The centre is the INTEGER pixel (u, v), the
+ *     pixel the visibility test looks up for this point: there a point always finds its own depth or a nearer one.  The
+ *     footprint is clipped to the frame; a point near the camera may cover all of it.
+ *   out[f][i][j] = the minimum over everything texel (i, j) was offered, 0 if it was offered nothing.
+ * Consequences:
+ *   wherever bff_render_depth_u16's frame holds a depth, this frame holds a value that is not larger;
+ *   the result is a minimum of integers: the frames do not depend on point order, frame tile or run;
+ *   only in-bounds points take part, so the culling by tile_bounds stays exact: the same frames with and without the table;
+ *   for the same reason a surface within a radius of the image border gets no help from points just outside the image:
+ *     texels there may stay empty although the surface continues;
+ *   the squares are flat (one depth per point), so on a surface tilted against the view a footprint reaches texels where
+ *     the surface itself lies farther, and the minimum is biased towards the camera by about the radius times the slope:
+ *     r should be about the cloud's point spacing, not larger.  Which value serves a dataset best is untuned. */
+int bff_render_splat_depth_u16(const double *xyz, int64_t n_points, int64_t n_pad, const double *inv_pose,
+                               const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width,
+                               int32_t depth_h, int32_t depth_w, double splat_radius, int32_t frames_per_block,
+                               uint32_t *scratch_u32, uint16_t *out_u16, const double *tile_bounds, void *stream);
+
+/* Texels of a point's footprint rectangle up to which the point's own lane walks it; a larger rectangle is walked by the
+ * whole wave. */
+int bff_splat_lane_box(void);
 
 /* ------------------------------------------------------------------------------------------
  * Depth frames rendered from a triangle mesh: what bff_render_depth_u16 supplies, without its holes (fine frames) and
