@@ -236,7 +236,8 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
     // 1e-6 and m exceed the float64 rounding of these forms (~1e-11) by orders of magnitude; NaN / inf corner
     // values compare false and keep the frame.  Exact: a skipped frame has no in-bounds point in this wave.
     uint64_t culled = 0;                                   // bit 8 k set: frame f0 + k cannot see this wave's points
-    if (tile_bounds) {
+    if (tile_bounds && __ballot(valid[0])) {               // the table has one box per tile that holds points (a wave's
+                                                           // first point is lane 0's; asking valid[] costs no register)
         const double *bb = tile_bounds + 6 * (word0 / kPPT);
         const int corner = lane & 7, fk = lane >> 3;
         const double bx = (corner & 1) ? bb[3] : bb[0], by = (corner & 2) ? bb[4] : bb[1], bz = (corner & 4) ? bb[5] : bb[2];
@@ -1194,6 +1195,15 @@ static int raw_depth_params(int32_t depth_h, int32_t depth_w, int32_t height, in
     return sensor_taps(depth_h, depth_w, height, width, tiled, st, &r->taps);
 }
 
+// The frame tile of a block: >= ~4096 blocks in flight, tiles of up to 8 frames (the culling ballot and the LDS mask
+// tables hold 8).  The one statement of the choice: the sweep and bff_count_viewed (frames_per_block == 0) ask here.
+extern "C" int32_t bff_sweep_frames_per_block(int64_t n_points, int32_t n_frames)
+{
+    if (n_points <= 0 || n_frames <= 0) return 1;
+    const int64_t fpb = (int64_t)n_frames * ceil_div(n_points, (int64_t)kPtsPerBlock) / 4096;
+    return fpb < 1 ? 1 : (fpb > 8 ? 8 : (int32_t)fpb);
+}
+
 static int project_views_launch(const double *xyz, int64_t n_points, int64_t n_pad,
                                 const double *inv_pose, const double *cam_intr_host, int32_t n_frames,
                                 const void *depth, const RawDepth *raw, const int32_t *depth_index, int32_t height, int32_t width,
@@ -1235,8 +1245,7 @@ static int project_views_launch(const double *xyz, int64_t n_points, int64_t n_p
     Intrinsics K;
     for (int i = 0; i < 9; ++i) K.k[i] = cam_intr_host[i];
     const int64_t gx = ceil_div(n_points, kPtsPerBlock);
-    int fpb = (int)((int64_t)n_frames * gx / 4096);      // keep >= ~4096 blocks in flight
-    fpb = fpb < 1 ? 1 : (fpb > 8 ? 8 : fpb);
+    const int fpb = bff_sweep_frames_per_block(n_points, n_frames);
     dim3 grid((unsigned)gx, (unsigned)ceil_div(n_frames, fpb));
     const int64_t seg_words = ceil_div(ceil_div((int64_t)height * width, 128), 32);
     const int64_t label_stride = bff_label_plane_stride((int64_t)height * width);
@@ -1365,10 +1374,7 @@ extern "C" int bff_count_viewed(const double *xyz, int64_t n_points, int64_t n_p
     for (int i = 0; i < 9; ++i) K.k[i] = cam_intr_host[i];
     const int64_t gx = ceil_div(n_points, kPtsPerBlock);
     int fpb = frames_per_block;
-    if (fpb == 0) {        // >= ~4096 blocks in flight, tiles of up to 8 frames (c2, 300 frames: 16 and 32 are slower)
-        fpb = (int)((int64_t)n_frames * gx / 4096);
-        fpb = fpb < 1 ? 1 : (fpb > 8 ? 8 : fpb);
-    }
+    if (fpb == 0) fpb = bff_sweep_frames_per_block(n_points, n_frames);     // c2, 300 frames: 16 and 32 are slower
     BFF_LIMIT(ceil_div(n_frames, fpb) <= 65535, "bff_count_viewed: too many frame tiles");
     dim3 grid((unsigned)gx, (unsigned)ceil_div(n_frames, fpb));
     if (depth_layout >= 0)

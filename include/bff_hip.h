@@ -32,7 +32,7 @@ extern "C" {
 #define BFF_E_ARG (-1)      /* null pointer / negative size / unsupported parameter */
 #define BFF_E_LIMIT (-2)    /* size beyond what a kernel supports (documented per call) */
 
-#define BFF_ABI_VERSION 14
+#define BFF_ABI_VERSION 15
 
 int bff_abi_version(void);
 const char *bff_last_error(void);
@@ -343,6 +343,11 @@ int bff_mesh_lane_box(void);
  * bit-identical with and without it.  It pays when the cloud is spatially sorted (scene.morton_order). */
 int bff_point_tile_bounds(const double *xyz, int64_t n_points, int64_t n_pad, double *bounds, void *stream);
 int bff_point_tile_size(void);
+
+/* Frames one block of bff_project_views / _u16 / _lookup visits (its frame tile) for a cloud of n_points and a list of
+ * n_frames: clamp(n_frames * ceil(n_points / 1024) / 4096, 1, 8), also bff_count_viewed's choice under
+ * frames_per_block == 0.  Read-only: results never depend on it; tests ask it to know which tile sizes they reach. */
+int32_t bff_sweep_frames_per_block(int64_t n_points, int32_t n_frames);
 
 /* Profiling aid.  bff_profile_next_sweep(start, stop): the next bff_project_views launch of the calling host
  * thread carries the two events on its dispatch (hipExtLaunchKernelGGL), so that bff_event_elapsed_ms(start,
