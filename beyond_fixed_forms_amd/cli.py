@@ -11,6 +11,9 @@ flight (`pipeline.project_stream`).  The refinement makes the class's one exchan
 (`distributed.ClassBatch`) and rank 0 writes the final files; the projection stage's files are the hand-over between
 the two processes and are written by the rank that produced them (their `final_class` strings come from that rank's
 mask_2d file), the class checkpoint by rank 0.
+
+The third stage, `evaluation_main` (the reference's evaluation/eval/eval_scannet200.py), scores a class's final files
+against the ground truth in one process: AP, AP50, AP25 and the recalls into the class's line of the results file.
 """
 from __future__ import annotations
 
@@ -21,6 +24,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -307,4 +311,61 @@ def refinement_main(argv=None):
                 write_scene_checkpoint("refinement", cls, ckpt)
     if ws > 1:
         _finish_ranks()
+    return 0
+
+
+def _evaluation_parser():
+    """eval_scannet200.py:29-32 plus what the reference hard-codes (:74-76) or imports from its dataset tables."""
+    p = argparse.ArgumentParser(description="Beyond-Fixed-Forms per-class evaluation (MI355X)")
+    p.add_argument("--cls", type=str, required=True, help="Specific class to evaluate")
+    p.add_argument("--config", type=str, default="configs/config.yaml", help="Config (final_output_dir is read from it)")
+    p.add_argument("--gt-dir", type=str, default="./data/Scannet200/Scannet200_3D/groundtruth",
+                   help="Directory of the ground-truth <scene>.pth files")
+    p.add_argument("--results-file", type=str, default="./evaluation/eval_results/overall_results.txt",
+                   help="Summary file whose line of this class is replaced")
+    p.add_argument("--label-table", type=str, required=True,
+                   help='JSON {"class_labels": [...], "semantic_ids": [...]}: the evaluator\'s class names and the '
+                        "dataset's raw semantic id of each")
+    return p
+
+
+def evaluation_main(argv=None):
+    """python tools/eval_scannet200.py --cls "<class>" --label-table labels.json            (eval_scannet200.py:70-148)
+    The class's final files against the ground truth: AP, AP50, AP25 and the recalls of the class into its line of the
+    results file, every label's into result.txt beside it."""
+    import json
+
+    from . import evaluation as ev
+    args = _evaluation_parser().parse_args(argv)
+    cfg = load_config(args.config)
+    with open(args.label_table, "r") as f:
+        table = json.load(f)
+    # semantic_ids is the dataset's whole list (BENCHMARK_SEMANTIC_IDXS: 200 ids, wall and floor first); the evaluator's
+    # `- 2 + 1` for scannet200 (EVAL:272-273) is what lines position p of it up with class_labels[p - 2]
+    labels, semantic_ids = list(table["class_labels"]), list(table["semantic_ids"])
+    cls = args.cls
+    data_path = os.path.join(cfg.final_output_dir, cls)
+    if not os.path.isdir(data_path):
+        print(f"no final output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
+        return 1
+    _lib.load()
+    _host_threads()
+    device = "cuda"
+    evaluator = ev.Evaluator(labels, device=device)
+    for scene in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):            # :77
+        loader = torch.load(os.path.join(args.gt_dir, scene), map_location="cpu", weights_only=False)
+        sem_gt = ev.semantic_positions(loader[2], semantic_ids)                             # :88-97
+        truth = evaluator.prepare_ground_truth(sem_gt, np.asarray(loader[3]).astype(np.int32))
+        result = torch.load(os.path.join(data_path, scene), map_location="cpu", weights_only=False)
+        preds, rows = ev.final_file_predictions(result, scene.replace(".pth", ""), labels, truth.n_points, device)
+        evaluator.add_scan(preds, ground_truth=truth, pred_rows=rows)
+    avgs = evaluator.evaluate()
+    results_dir = os.path.dirname(os.path.abspath(args.results_file))
+    os.makedirs(results_dir, exist_ok=True)
+    ev.write_result_file(avgs, evaluator.eval_class_labels, os.path.join(results_dir, "result.txt"))   # EVAL:597
+    if cls not in avgs["classes"]:
+        raise KeyError(f"class {cls!r} is not in the label table")                         # :142
+    print(ev.format_results(avgs, [cls]), end="")
+    ev.update_results_file(args.results_file, cls, [avgs["classes"][cls][k] for k in
+                                                    ("ap", "ap50%", "ap25%", "rc", "rc50%", "rc25%")], labels)
     return 0
