@@ -32,7 +32,7 @@ inline int launched(const char *what) {
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+__host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // bff_scene_project clears every scratch buffer of its steps with ONE fill (they are laid out in one block,
 // bff_scene_workspace) and sets this flag for the duration of the call: the steps' own clears become no-ops.
@@ -51,7 +51,7 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 
 __device__ __forceinline__ int popc64(uint64_t v) { return __popcll(v); }
 
-// Run starts and ends of word w of a bit row (rows.hip: bit rows -> 1-D RLE; masks2d.hip: bit planes -> run tables).
+// Run starts and ends of word w of a bit row (row_codec.hip: bit rows -> 1-D RLE; masks2d.hip: bit planes -> run tables).
 // A run starts at point p iff bit p is set and bit p-1 is not; it ends (exclusive) at e iff bit e-1 is set and bit e
 // is not.  Padding bits are zero and word nw is a virtual zero word, so a run reaching the last point ends like any other.
 __device__ __forceinline__ void rle_word_edges(const uint64_t *row, int64_t w, int64_t nw, uint64_t &starts,

@@ -7,18 +7,9 @@
 //   decode -> sweep -> point filter threshold -> keep bits -> row statistics -> tile order -> components ->
 //   groups (device) -> OR of members + confidence means -> (rows recycled) -> overlaps + filter + counts ->
 //   caller point order -> stage-1 decode -> stage-1 x (stage-2 | stage-1) intersections -> header to the host
-#include "common.h"
+#include "rows.h"
 
 using namespace bff;
-
-namespace bff {
-int merge_components_streams(const uint64_t *rows, int32_t n_rows, int64_t nw, const int32_t *order,
-                             int32_t n_order, const uint64_t *chunk_mask, uint64_t *tile_mask,
-                             const uint32_t *hist, uint32_t *scratch, const int32_t *area,
-                             const int32_t *label_id, float iou_thres, int32_t *parent, int32_t init_parent,
-                             int32_t *comp, int32_t *diag, const uint16_t *chunk_pop, void *stream, void *heavy_stream,
-                             void *before_heavy, void *after_heavy);
-}
 
 namespace {
 

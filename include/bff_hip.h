@@ -436,8 +436,8 @@ int bff_merge_adjacency(const uint64_t *rows, int32_t n_rows, int64_t nw, const 
  * i's component.  Rows with an empty
  * adjacency row (area 0, or thr >= 1) form singleton components here; the host turns them into the
  * reference's empty lists (it knows area and thr).  All other arguments as for bff_merge_adjacency;
- * chunk_mask, tile_mask and hist are required; scratch: uint32 [bff_merge_scratch_words(n_rows)] (sorted histograms,
- * tile bounds, position-indexed row tables, the two tile-pair lists).
+ * chunk_mask, tile_mask and hist are required; scratch: uint32 [bff_merge_scratch_words(n_rows)], 8-byte aligned
+ * (sorted histograms, tile bounds, position-indexed row tables, the two tile-pair lists; layout: merge.hip, MergeScratch).
  * Inside a tile pair the block keeps disjoint sets of its 128 rows in LDS (started from the global forest): every
  * few chunks it settles the pairs whose PARTIAL intersection already passes the IoU test (the float32 expression is
  * monotone in I, so the edge exists) or whose rows have become connected meanwhile, and stops as soon as no pair is
@@ -497,7 +497,7 @@ int bff_group_conf_mean(const void *conf, int32_t dtype, const int32_t *group_of
  *   solve_overlapping P:277-301 on `rows` in place.  The reference visits the pairs (i < j) that overlap before any
  *     edit in (i, j) order; the row merged from fewer raw masks (size[], ties: row i) loses the points of the other.
  *     For a single point that walk is a champion scan over the rows holding it, so the point ends up in exactly one of
- *     them: the one with the largest size, among equals the largest index (derivation: rows.hip,
+ *     them: the one with the largest size, among equals the largest index (derivation: resolve.hip,
  *     resolve_priority_kernel) -- an exclusive prefix OR over the rows in that order, no intersections needed;
  *   rows[i] &= keep (P:595; keep may be NULL);  after[i] = popcount(rows[i])  (P:596).
  * The literal ordered replay stays available as bff_overlap_ops + bff_apply_row_ops (tests compare the two). */

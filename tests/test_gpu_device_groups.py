@@ -1,4 +1,4 @@
-"""GPU parity of the scene call's tail (csrc/rows.hip), entry point by entry point: groups formed on the device
+"""GPU parity of the scene call's tail (csrc/groups.hip, resolve.hip, rows.hip), entry point by entry point: groups formed on the device
 (bff_group_components), their OR and confidence means (bff_or_reduce_grouped), the arena clear
 (bff_clear_flagged_chunks_unless), and the steps that read the group count on the device (bff_resolve_overlaps_dev,
 bff_scatter_bits, bff_cross_popcount_dev) -- against plain NumPy / the oracle, at the sizes and counts where their

@@ -1,6 +1,6 @@
 """bff_merge_components path by path, and bff_row_stats, against the NumPy reference of tests/merge_ref.py.
 
-Every path of the tile pass (rows.hip: tile_masks_kernel -> tile_pair_filter_kernel -> tile_pair_rows_kernel ->
+Every path of the tile pass (merge.hip: tile_masks_kernel -> tile_pair_filter_kernel -> tile_pair_rows_kernel ->
 merge_components_kernel / merge_tile_pair) is reached at a size that takes seconds: the pair-list and the dense 4x4
 accumulation, split mode (several blocks per tile pair that meet in a scratch slot), the "out of slots" fallback, the
 chunk-level bound, a sampled order and a continued forest.  The inputs put many pairs within a few points of the
@@ -22,7 +22,7 @@ import merge_ref as mr
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
-# Restated from rows.hip (kSplitStages, kKW, kCW, kMaxSlots, kSparse); used only for preconditions on the inputs.
+# Restated from merge.hip (kSplitStages, kKW, kCW, kMaxSlots, kSparse); used only for preconditions on the inputs.
 PART_CHUNKS = 12 * (32 // 8)        # kSplitStages * (kKW / kCW): chunks per part of a split tile pair
 SPLIT_MIN = 2 * PART_CHUNKS         # tile pairs that share >= 96 chunks are split
 MAX_SLOTS = 512                     # kMaxSlots: tile pairs that can be split in one call
@@ -268,12 +268,13 @@ def get_case(name, *args):
 
 # ---- running the kernel -----------------------------------------------------------------------------------------------
 
-def run_merge(lib, c, order, diag=False, chunk_pop=None, parent=None, init_parent=1, n_order=None):
+def run_merge(lib, c, order, diag=False, chunk_pop=None, parent=None, init_parent=1, n_order=None, scratch=None):
     """bff_merge_components called directly -> (comp, diag counters or None)."""
     dv = c.device(lib)
     i32, i64 = torch.int32, torch.int64
     tmask = torch.empty(((c.r + 63) // 64, dv["cmask"].shape[1]), dtype=i64, device=DEV)
-    scratch = torch.empty(int(lib.load().bff_merge_scratch_words(c.r)), dtype=i32, device=DEV)
+    if scratch is None:
+        scratch = torch.empty(int(lib.load().bff_merge_scratch_words(c.r)), dtype=i32, device=DEV)
     parent = torch.empty(c.r, dtype=i32, device=DEV) if parent is None else parent
     comp = torch.full((c.r,), -7, dtype=i32, device=DEV)
     dg = torch.zeros(16, dtype=i32, device=DEV) if diag else None
@@ -490,6 +491,28 @@ def test_split_switched_off_in_a_fresh_process(lib):
         assert 0 < got["diag"][0] <= n_tile_pairs(c.r)              # one block per tile pair: nothing was split
         print(f"(g) split off order={name}: diag[0]={got['diag'][0]} [2]={got['diag'][2]} [9]={got['diag'][9]} "
               f"[10]={got['diag'][10]}")
+
+
+# ---- scratch layout: nothing is written behind bff_merge_scratch_words ------------------------------------------------
+
+GUARD_WORDS, GUARD = 256, 0x5A5A5A5A
+
+
+@pytest.mark.parametrize("which", ["split", "pair_list"])
+def test_scratch_guard_words_untouched(lib, which):
+    """The scratch buffer is exactly bff_merge_scratch_words(n_rows) words, followed by guard words: the call leaves the
+    guard alone and finds the reference's components.  Split mode is the one path that writes the regions at the end of
+    the layout (arrival counters, partial counts); the pair-list input is the plain path."""
+    c = get_case("bernoulli", 128, 65_536 + 77, 13) if which == "split" else get_case("pair_list", 130, 11)
+    words = int(lib.load().bff_merge_scratch_words(c.r))
+    for name, order in c.orders(lib):
+        for diag in (False, True):
+            buf = torch.full((words + GUARD_WORDS,), GUARD, dtype=torch.int32, device=DEV)
+            comp, dg = run_merge(lib, c, order, diag=diag, scratch=buf[:words])
+            assert np.array_equal(comp, c.comp), name
+            assert (buf[words:] == GUARD).all().item(), name
+            if diag and which == "split":
+                assert dg[0] > n_tile_pairs(c.r), name                  # parts ran: the end regions were in use
 
 
 # ---- (h) bff_row_stats -------------------------------------------------------------------------------------------------

@@ -83,6 +83,20 @@ def test_size_limits_are_rejected_on_the_host():
     assert lib.bff_resolve_overlaps_dev(p, 4097, 10, p, None, p, p, p, None) == -2 and b"4096 rows" in lib.bff_last_error()
 
 
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 127, 128, 129, 640, 2047, 2048, 4096, 20000])
+def test_merge_scratch_words_formula(n):
+    """bff_merge_scratch_words sizes the scene workspace and its one fill: the figure is fixed, region by region (merge.hip,
+    MergeScratch), with the 2 + 4 spare words it has always had."""
+    from beyond_fixed_forms_amd import _lib
+    k_t, k_bins, k_max_parts, k_max_slots = 64, 64, 8, 512
+    nt = (max(n, 1) + k_t - 1) // k_t
+    n_pos, total = nt * k_t, nt * (nt + 1) // 2
+    cap2 = total + (k_max_parts - 1) * min(total, k_max_slots)
+    want = (k_bins // 2) * n_pos + k_bins * nt + nt + 3 * n_pos + 4 + total + cap2 + 4 * cap2 + 2 + cap2 + 4 + \
+        k_max_slots * (k_t * k_t + 1)
+    assert _lib.load().bff_merge_scratch_words(n) == want
+
+
 def test_no_cpu_fallback():
     from beyond_fixed_forms_amd import _lib
     with pytest.raises(ValueError):

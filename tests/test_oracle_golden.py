@@ -178,7 +178,7 @@ def test_evaluation_assignment_restatement(name):
 
 @pytest.mark.parametrize("seed", range(12))
 def test_ordered_overlap_loop_has_a_closed_form(seed):
-    """What the device's one-pass overlap resolution relies on (rows.hip, resolve_priority_kernel): after the reference's
+    """What the device's one-pass overlap resolution relies on (resolve.hip, resolve_priority_kernel): after the reference's
     ordered pair loop (P:277-301) every point that was in some row is in exactly one of them -- the one merged from the most
     raw masks, among equals the one with the LARGEST index.  Checked here against the oracle's literal loop: random
     rows from sparse to nearly full, sizes with many ties, also all sizes equal and strictly increasing / decreasing."""
