@@ -34,6 +34,10 @@ SIGNATURES = {
     "bff_count_viewed": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _I, _P, _P, _P],
     "bff_render_depth_u16": [_P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "bff_render_splat_depth_u16": [_P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _D, _I, _P, _P, _P, _P],
+    "bff_point_labels": [_P, _I, _L, _L, _P, _P, _P],
+    "bff_render_labels_u16": [_P, _L, _L, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _P, _P, _P, _P, _P],
+    "bff_label_runs_count": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "bff_label_runs_emit": [_P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P],
     "bff_render_mesh_depth_u16": [_P, _L, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "bff_render_mesh_depth_clip_u16": [_P, _L, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _D, _I, _P, _P, _P],
     "bff_popcount_rows": [_P, _P, _I, _L, _P, _P],
@@ -82,7 +86,7 @@ SIGNATURES = {
     "bff_depth_from_u16": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P],
 }
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
-         "bff_masks2d_tile_pixels": (c_int32, []), "bff_mask_lookup_rows": (c_int32, [c_int32, c_int32, c_int64]),
+         "bff_masks2d_tile_pixels": (c_int32, []), "bff_label_runs_tile_pixels": (c_int32, []), "bff_mask_lookup_rows": (c_int32, [c_int32, c_int32, c_int64]),
          "bff_chunk_mask_words": (c_int32, [c_int64]), "bff_label_plane_stride": (c_int64, [c_int64]), "bff_resolve_overlaps_max_rows": (c_int32, []),
          "bff_point_tile_size": (c_int32, []), "bff_sweep_frames_per_block": (c_int32, [c_int64, c_int32]), "bff_mesh_lane_box": (c_int32, []), "bff_splat_lane_box": (c_int32, []), "bff_depth_tiled_texels": (c_int64, [c_int32, c_int32]), "bff_merge_scratch_words": (c_int64, [c_int32]), "bff_merge_uses_chunk_bound": (c_int32, [c_int64]),
          "bff_profile_next_merge": (c_int32, [_P, _P]), "bff_group_slice_cap": (c_int32, [c_int32, c_int32]),
@@ -91,7 +95,7 @@ PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, [
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class BffLibraryError(RuntimeError):
@@ -425,6 +429,69 @@ def render_mesh_depth(vertices_soa, n_vertices, faces, inv_pose, cam_intr, heigh
         else:
             call("bff_render_mesh_depth_u16", *head, *tail)
     return out
+
+
+MAX_POINT_LABEL = 65534            # labels of bff_render_labels_u16 (65535 << 16 | 65535 is its empty key)
+
+
+def point_labels(rows, n_points, unsort=None):
+    """Instance bit rows int64 [K][nw] in the caller's point order -> int16 [n_points] holding the uint16 label of every
+    point: 1 + the first row that holds it, 0 = none (bff_point_labels).  unsort (int32 [n_points]): the label of
+    original point o goes to position unsort[o], the sorted cloud's order."""
+    if rows.dim() != 2:
+        raise ValueError("point_labels: rows must be [K][nw]")
+    lab = torch.empty(max(int(n_points), 1), dtype=torch.int16, device=rows.device)[:int(n_points)]
+    call("bff_point_labels", _ptr(rows, i64) if rows.numel() else None, int(rows.shape[0]), int(rows.shape[1]), int(n_points),
+         _ptr(unsort, i32), _ptr(lab))
+    return lab
+
+
+def render_labels(xyz_soa, n_points, lab, inv_pose, cam_intr, height, width, depth_h, depth_w, tile_bounds=None,
+                  frames_per_block=0, scratch_texels=None, splat_radius=0.0, want_depth=False):
+    """The label z-buffer (bff_render_labels_u16): render_depth's frames with the label of the nearest point next to its
+    millimetres.  lab: int16 [n_points] as point_labels returns it, in the order of xyz_soa.  -> (labels, depth or None),
+    int16 [F][depth_h][depth_w] each (the uint16 values); depth, when asked for, is render_depth's frame for the same
+    arguments byte for byte.  Scratch cap and frame runs are render_depth's."""
+    if lab.shape[0] != n_points:
+        raise ValueError(f"render_labels: {lab.shape[0]} labels for {n_points} points")
+    k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
+    f, plane = int(inv_pose.shape[0]), int(depth_h) * int(depth_w)
+    dev = xyz_soa.device
+    labels = torch.empty((f, int(depth_h), int(depth_w)), dtype=torch.int16, device=dev)
+    depth = torch.empty_like(labels) if want_depth else None
+    per = max(1, min(f, (RENDER_SCRATCH_TEXELS if scratch_texels is None else int(scratch_texels)) // max(plane, 1)))
+    scratch = torch.empty(max(per * plane, 1), dtype=i32, device=dev)
+    for f0 in range(0, max(f, 1), per):
+        f1 = min(f, f0 + per)
+        call("bff_render_labels_u16", _ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(lab, torch.int16) if n_points else None,
+             _ptr(inv_pose[f0:f1], f64), ctypes.cast(k, c_void_p), f1 - f0, int(height), int(width), int(depth_h), int(depth_w),
+             float(splat_radius), int(frames_per_block), _ptr(scratch), _ptr(labels[f0:f1]),
+             None if depth is None else _ptr(depth[f0:f1]), _ptr(tile_bounds, f64))
+    return labels, depth
+
+
+def label_runs_count(labels, height, width, n_labels):
+    """Label frames int16 [F][dh][dw] (uint16 values) -> (n_runs, n_pix) int32 [F][n_labels]: runs and pixels of every
+    (frame, label) of the image upsampled to (height, width) (bff_label_runs_count)."""
+    f, dh, dw = labels.shape
+    n_runs = torch.empty((f, n_labels), dtype=i32, device=labels.device)
+    n_pix = torch.empty((f, n_labels), dtype=i32, device=labels.device)
+    call("bff_label_runs_count", _ptr(labels, torch.int16), f, dh, dw, int(height), int(width), int(n_labels), _ptr(n_runs),
+         _ptr(n_pix))
+    return n_runs, n_pix
+
+
+def label_runs_emit(labels, height, width, mask_index, total_runs):
+    """-> (start_keys, end_keys) int64 [total_runs], unordered: (mask << 31) | position of every run of the masks
+    mask_index (int32 [F][n_labels], -1 = none) names (bff_label_runs_emit)."""
+    f, dh, dw = labels.shape
+    dev = labels.device
+    start_keys = torch.empty(total_runs, dtype=i64, device=dev)
+    end_keys = torch.empty(total_runs, dtype=i64, device=dev)
+    cursor = torch.empty(2, dtype=i32, device=dev)
+    call("bff_label_runs_emit", _ptr(labels, torch.int16), f, dh, dw, int(height), int(width), int(mask_index.shape[1]),
+         _ptr(mask_index, i32), int(total_runs), _ptr(cursor), _ptr(start_keys), _ptr(end_keys))
+    return start_keys, end_keys
 
 
 def tile_depth(raw, metres=True):

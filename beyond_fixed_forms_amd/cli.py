@@ -314,6 +314,79 @@ def refinement_main(argv=None):
     return 0
 
 
+def _reproject_parser():
+    p = _parser("Beyond-Fixed-Forms 3D->2D reprojection: a class's instances as 2-D masks of the colour frames (MI355X)")
+    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
+                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
+    p.add_argument("--every", type=int, default=None,
+                   help="Render into every n-th colour frame (default: downsample_ratio, the frames the 2-D stage saw)")
+    return p
+
+
+def _saved_instances(result, n_points, device):
+    """A saved stage file {"ins", "conf", "final_class"} -> what reproject.instance_masks_2d reads: bit rows on the
+    device, confidences, class strings (the reference's list-valued empty forms give no rows)."""
+    from types import SimpleNamespace
+    ins, classes = result["ins"], result["final_class"]
+    classes = [str(c) for c in (classes.reshape(-1).tolist() if torch.is_tensor(classes) else classes)]
+    if isinstance(ins, (list, tuple)) and len(ins) and isinstance(ins[0], dict):
+        from .scene import runs_from_rles
+        if any(int(r["length"]) != n_points for r in ins):
+            raise ValueError("RLE instances of another length than the cloud")
+        t = lambda a: torch.from_numpy(a).to(device)
+        rows = _lib.rle_to_rows(*[t(a) for a in runs_from_rles(ins, "instance")], n_points)
+    else:
+        ins = torch.as_tensor(ins)
+        if ins.dim() != 2 or ins.shape[0] == 0 or ins.shape[1] != n_points or not classes:
+            return SimpleNamespace(rows=None, conf=[], final_class=[])
+        rows = _lib.pack_rows((ins.to(device) == 1).contiguous())
+    return SimpleNamespace(rows=rows, conf=result["conf"], final_class=classes)
+
+
+def reproject_main(argv=None):
+    """python tools/reproject_3d_to_2d.py --config configs/config.yaml --cls "<class>" [--stage final|mask_3d] [--every n]
+    For every scene of the class's output directory: its instances rendered into every n-th colour frame
+    (reproject.instance_masks_2d) and saved to reprojected_2d_dir/<cls>/<scene>.pth in the mask_2d file format (RLE
+    dicts).  Only the intrinsics, the poses and the cloud are read -- no depth frame."""
+    from types import SimpleNamespace
+
+    from . import masks2d, reproject
+    from .io import read_matrix_txt
+    from .scene import viewed_frame_ids
+    args = _reproject_parser().parse_args(argv)
+    cfg = load_config(args.config)
+    cls = args.cls
+    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
+    if not os.path.isdir(data_path):
+        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
+        return 1
+    out_dir = cfg.get("reprojected_2d_dir")
+    if not out_dir:
+        raise ValueError("reprojected_2d_dir is not set in the config")
+    every = int(cfg.downsample_ratio) if args.every is None else int(args.every)
+    if every < 1:
+        raise ValueError(f"--every must be >= 1, got {every}")
+    _lib.load()
+    _host_threads()
+    device = "cuda"
+    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
+        scene_id = name[:-4]
+        print("Working on", scene_id, "class", cls)
+        scene_dir = os.path.join(cfg.scene_2d_dir, scene_id)
+        color_dir = os.path.join(scene_dir, "color")
+        color_files = [f for f in os.listdir(color_dir) if f.endswith(".jpg")] if os.path.isdir(color_dir) else []
+        frame_ids = viewed_frame_ids(color_files, every)
+        scene = SimpleNamespace(scene_id=scene_id, points=np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy")),
+                                cam_intr=read_matrix_txt(os.path.join(scene_dir, "intrinsic", "intrinsic_color.txt")),
+                                poses={f: read_matrix_txt(os.path.join(scene_dir, "pose", f"{f}.txt")) for f in frame_ids})
+        geom = reproject.geometry_for_frames(scene, cfg, frame_ids, device)
+        # the stage's own output file, written by this project's scripts or the reference's (a pickled dict of tensors)
+        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+        masks = reproject.instance_masks_2d(geom, frame_ids, _saved_instances(result, geom.n_points, device), cfg)
+        save_result(masks2d.encode_2d_masks(masks), out_dir, cls, scene_id)
+    return 0
+
+
 def _evaluation_parser():
     """eval_scannet200.py:29-32 plus what the reference hard-codes (:74-76) or imports from its dataset tables."""
     p = argparse.ArgumentParser(description="Beyond-Fixed-Forms per-class evaluation (MI355X)")

@@ -32,6 +32,13 @@ DEFAULTS = dict(
     # a camera-facing square of this half-width instead of one texel (scene.cloud_splat_radius): near surfaces close their
     # own gaps.  0 = off, the frames as they were.  About the cloud's point spacing; no value has been tuned
     cloud_splat_radius=0.0,
+    # not keys of the reference either: rendering 3-D instances back into the views (reproject.py,
+    # tools/reproject_3d_to_2d.py).  reproject_stride: integer s >= 1, the label frames are rendered at (ceil(height_2d / s),
+    # ceil(width_2d / s)) and upsampled by the integer map; reproject_splat_radius: metres >= 0, the footprint of a point
+    # (about the cloud's point spacing, untuned; flat surfels bleed a label by about one radius at silhouettes), 0 = one
+    # texel per point; reproject_min_pixels: an instance covering fewer pixels of a frame makes no mask there;
+    # reprojected_2d_dir: where the tool saves <cls>/<scene>.pth
+    reproject_stride=1, reproject_splat_radius=0.0, reproject_min_pixels=1, reprojected_2d_dir=None,
 )
 
 

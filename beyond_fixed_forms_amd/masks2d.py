@@ -179,11 +179,21 @@ def to_device_runs(masks_2d, device=None):
 
 def encode_2d_masks(masks_2d, device=None):
     """Drop-in for encode_2d_masks (RLE:63-80): every entry's dense `segmented_frame_masks` becomes its list of RLE
-    dicts, in place, with one read-back for the whole list; entries that already hold RLE dicts are left alone."""
+    dicts, in place, with one read-back for the whole list; entries that already hold RLE dicts are left alone.  An entry
+    that holds DeviceRuns (to_device_runs, reproject.instance_masks_2d) becomes RLE dicts too: one read-back per call
+    whose tables the entries view."""
     idx = [i for i, fr in enumerate(masks_2d) if is_dense(fr["segmented_frame_masks"])]
     if idx:
         runs = _encode([masks_2d[i]["segmented_frame_masks"] for i in idx], device)
         rles = runs.to_rles()
         for i, a, b in zip(idx, runs.frame_offs[:-1], runs.frame_offs[1:]):
             masks_2d[i]["segmented_frame_masks"] = rles[a:b]
+    fetched = {}
+    for fr in masks_2d:
+        d = fr["segmented_frame_masks"]
+        if isinstance(d, DeviceRuns):
+            own = d.owner if d.owner is not None else d
+            if id(own) not in fetched:
+                fetched[id(own)] = own.to_rles()
+            fr["segmented_frame_masks"] = fetched[id(own)][d.first_mask:d.first_mask + len(d)]
     return masks_2d

@@ -32,7 +32,7 @@ extern "C" {
 #define BFF_E_ARG (-1)      /* null pointer / negative size / unsupported parameter */
 #define BFF_E_LIMIT (-2)    /* size beyond what a kernel supports (documented per call) */
 
-#define BFF_ABI_VERSION 15
+#define BFF_ABI_VERSION 16
 
 int bff_abi_version(void);
 const char *bff_last_error(void);
@@ -258,6 +258,66 @@ int bff_render_splat_depth_u16(const double *xyz, int64_t n_points, int64_t n_pa
 /* Texels of a point's footprint rectangle up to which the point's own lane walks it; a larger rectangle is walked by the
  * whole wave. */
 int bff_splat_lane_box(void);
+
+/* ------------------------------------------------------------------------------------------
+ * 3-D instances rendered back into the views as 2-D masks: instance bit rows -> one label per point (bff_point_labels)
+ * -> a point z-buffer that carries the label next to the depth (bff_render_labels_u16) -> run tables of the label image
+ * at the working resolution (bff_label_runs_count / bff_label_runs_emit), the form bff_rle_to_maskbits and
+ * bff_mask_row_directory read 2-D masks in.
+ *
+ * bff_point_labels: rows uint64 [n_rows][nw] (nw >= ceil(n_points / 64)) in the caller's point order;
+ *   lab[p] = 1 + min{k : bit p of row k is set}, 0 when no row holds point p: priority is row order.
+ *   unsort (optional, int32 [n_points], a permutation as DeviceScene.unsort): the value of point o is written to
+ *   lab[unsort[o]] instead of lab[o], i.e. lab comes out in the sorted cloud's order (an entry outside [0, n_points) writes
+ *   nothing).  lab: uint16 [n_points].  n_rows <= 65534, more is BFF_E_LIMIT. */
+int bff_point_labels(const uint64_t *rows, int32_t n_rows, int64_t nw, int64_t n_points, const int32_t *unsort,
+                     uint16_t *lab, void *stream);
+
+/* bff_render_labels_u16: the point z-buffer of bff_render_depth_u16 (splat_radius == 0) or of bff_render_splat_depth_u16
+ * (splat_radius > 0) with a label per point.  Which points take part, their u, v, m = rint(c_2 * 1000.0), own texel,
+ * footprint rectangle and sample points are exactly that call's, operation by operation; every argument not named here,
+ * the early returns and the limits are that call's too.
+ *   splat_radius  metres: 0 or a finite double > 0; NaN, a negative value or inf is BFF_E_ARG (> 0: K00 and K11 must be
+ *                 finite and > 0 as there)
+ *   lab           uint16 [n_points] in the order of xyz (bff_point_labels with the scene's unsort), every value <= 65534
+ *   A point offers  key = (m << 16) | lab[n]  to each texel where the depth renderer offers m.  scratch_u32 (uint32
+ *   [n_frames][depth_h * depth_w], set to all ones by the call) keeps the unsigned minimum of the keys; a narrowing kernel
+ *   writes the key's low half to labels_u16 [n_frames][depth_h][depth_w] and its high half to depth_u16 (same shape, may be
+ *   NULL); a texel that was offered nothing holds 0 in both.
+ * Consequences:
+ *   the nearest surface wins whether it carries an instance or not: background points (lab 0) occlude;
+ *   at equal millimetres the smaller label wins: background before instance 0 before instance 1;
+ *   depth_u16 equals the frame the matching depth renderer produces for the same arguments, byte for byte (m sits in the
+ *     key's high half, so the minimum key holds the minimum m);
+ *   the result is a minimum of integers: it does not depend on point order, frame tile, culling table or run;
+ *   the flat surfels of splat_radius > 0 bleed a label by about one radius across a silhouette (the footprint of a near
+ *     point reaches texels where only a farther surface lies, and the near key wins there).
+ * Limits: bff_render_depth_u16's, and lab <= 65534 (65535 at m = 65535 would be the empty key). */
+int bff_render_labels_u16(const double *xyz, int64_t n_points, int64_t n_pad, const uint16_t *lab, const double *inv_pose,
+                          const double *cam_intr_host, int32_t n_frames, int32_t height, int32_t width, int32_t depth_h,
+                          int32_t depth_w, double splat_radius, int32_t frames_per_block, uint32_t *scratch_u32,
+                          uint16_t *labels_u16, uint16_t *depth_u16, const double *tile_bounds, void *stream);
+
+/* Label image -> run tables at the working resolution, without a dense plane per instance.
+ *   labels  uint16 [n_frames][depth_h][depth_w]; the upsampled image  up[f][v][u] = labels[f][(v * depth_h) / height]
+ *           [(u * depth_w) / width]  (the renderer's own integer map, inverted) is never materialised
+ *   Label L in [1, n_labels] of frame f: its runs are the maximal intervals [start, end) of the flat index p = v * width
+ *   + u with up == L (they may cross a row end, as bff_masks2d_runs emits them).  Labels above n_labels are ignored.
+ * bff_label_runs_count: n_runs, n_pix int32 [n_frames][n_labels] (entry (f, L - 1); cleared by the call) receive the
+ *   number of runs and of pixels of every (f, L): integer atomics, exact on every run.
+ * The caller decides which (f, L) become masks (pixel count >= its threshold), numbers them in (f, L) order into
+ *   mask_index int32 [n_frames][n_labels] (-1 = no mask) and sums their run counts to total_runs.
+ * bff_label_runs_emit: every run of a mask m appends (m << 31) | start to start_keys and (m << 31) | end to end_keys
+ *   (int64 [total_runs] each; cursor: uint32 [2] scratch, cleared by the call).  The order inside the two lists depends on
+ *   the run; as sets they are a function of the label image, and sorted ascending (bff_argsort_i64) the i-th start and the
+ *   i-th end belong to one run and the runs stand in mask order, ascending inside a mask: the low 31 bits are the tables.
+ * Limits: height * width < 2^31, depth_h * depth_w < 2^31, total_runs < 2^31, n_frames <= 65535, n_labels <= 65534. */
+int32_t bff_label_runs_tile_pixels(void);                          /* pixels of a frame per block of both passes */
+int bff_label_runs_count(const uint16_t *labels, int32_t n_frames, int32_t depth_h, int32_t depth_w, int32_t height,
+                         int32_t width, int32_t n_labels, int32_t *n_runs, int32_t *n_pix, void *stream);
+int bff_label_runs_emit(const uint16_t *labels, int32_t n_frames, int32_t depth_h, int32_t depth_w, int32_t height,
+                        int32_t width, int32_t n_labels, const int32_t *mask_index, int64_t total_runs, uint32_t *cursor,
+                        int64_t *start_keys, int64_t *end_keys, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Depth frames rendered from a triangle mesh: what bff_render_depth_u16 supplies, without its holes (fine frames) and
