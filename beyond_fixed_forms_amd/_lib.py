@@ -84,6 +84,15 @@ SIGNATURES = {
     "bff_sort_f32": [_P, _P, _L, _P, _P, _P],
     "bff_argsort_i64": [_P, _P, _P, _I, _I, _P, _P, _P],
     "bff_depth_from_u16": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P],
+    "bff_voxel_bounds": [_P, _L, _L, _P, _P],
+    "bff_voxel_keys": [_P, _L, _L, _P, _P, _D, _P, _P],
+    "bff_voxel_heads": [_P, _L, _P, _P],
+    "bff_voxel_ranks": [_P, _P, _P, _L, _L, _P, _P, _P],
+    "bff_voxel_neighbours": [_P, _L, _P, _P],
+    "bff_split_occupancy": [_P, _I, _L, _L, _P, _L, _P, _P, _P, _P],
+    "bff_split_union": [_P, _P, _P, _I, _L, _P, _I, _P, _P],
+    "bff_split_count": [_P, _I, _L, _L, _P, _L, _P, _P, _P, _P, _I, _I, _P, _P, _P],
+    "bff_split_emit": [_P, _I, _L, _L, _P, _L, _P, _P, _P, _P, _I, _P, _I, _P, _P],
 }
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
          "bff_masks2d_tile_pixels": (c_int32, []), "bff_label_runs_tile_pixels": (c_int32, []), "bff_mask_lookup_rows": (c_int32, [c_int32, c_int32, c_int64]),

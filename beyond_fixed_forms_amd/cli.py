@@ -14,6 +14,8 @@ mask_2d file), the class checkpoint by rank 0.
 
 The third stage, `evaluation_main` (the reference's evaluation/eval/eval_scannet200.py), scores a class's final files
 against the ground truth in one process: AP, AP50, AP25 and the recalls into the class's line of the results file.
+Beside the path: `reproject_main` renders a stage's instances back into the colour frames as 2-D masks, `split_main` cuts
+them into their spatially connected parts; each writes to a directory of its own.
 """
 from __future__ import annotations
 
@@ -384,6 +386,52 @@ def reproject_main(argv=None):
         result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
         masks = reproject.instance_masks_2d(geom, frame_ids, _saved_instances(result, geom.n_points, device), cfg)
         save_result(masks2d.encode_2d_masks(masks), out_dir, cls, scene_id)
+    return 0
+
+
+def _split_parser():
+    p = _parser("Beyond-Fixed-Forms 3-D instances split into spatially connected parts (MI355X)")
+    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
+                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
+    return p
+
+
+def split_main(argv=None):
+    """python tools/split_instances_3d.py --config configs/config.yaml --cls "<class>" [--stage final|mask_3d]
+    For every scene of the class's output directory: the cloud binned into a voxel grid of split_voxel metres once, every
+    instance cut into its connected parts (spatial.split_instances) and saved to split_output_dir/<cls>/<scene>.pth in the
+    stage's own file format, with the parts' parent instances under the added key "parent".  Only the cloud is read."""
+    from . import spatial
+    args = _split_parser().parse_args(argv)
+    cfg = load_config(args.config)
+    cls = args.cls
+    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
+    if not os.path.isdir(data_path):
+        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
+        return 1
+    out_dir = cfg.get("split_output_dir")
+    if not out_dir:
+        raise ValueError("split_output_dir is not set in the config")
+    cell = spatial.split_voxel(cfg)
+    spatial.split_min_points(cfg), spatial.split_mode(cfg)              # a bad value stops the run before the first scene
+    _lib.load()
+    _host_threads()
+    device = "cuda"
+    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
+        scene_id = name[:-4]
+        print("Working on", scene_id, "class", cls)
+        grid = spatial.voxel_grid(np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy")), cell, device)
+        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+        inst = _saved_instances(result, grid.n_points, device)
+        if inst.rows is None:                                            # the reference's empty forms pass through
+            save_result(result, out_dir, cls, scene_id)
+            continue
+        parts = spatial.split_instances(grid, inst, cfg)
+        ins = _lib.rows_to_rle(parts.rows, grid.n_points) if os.environ.get("BFF_SAVE_RLE") == "1" else \
+            _lib.unpack_rows(parts.rows, grid.n_points).cpu()
+        conf = parts.conf.cpu() if torch.is_tensor(parts.conf) else parts.conf
+        save_result({"ins": ins, "conf": conf, "final_class": parts.final_class, "parent": parts.parent}, out_dir, cls,
+                    scene_id)
     return 0
 
 

@@ -39,6 +39,12 @@ DEFAULTS = dict(
     # texel per point; reproject_min_pixels: an instance covering fewer pixels of a frame makes no mask there;
     # reprojected_2d_dir: where the tool saves <cls>/<scene>.pth
     reproject_stride=1, reproject_splat_radius=0.0, reproject_min_pixels=1, reprojected_2d_dir=None,
+    # not keys of the reference either: 3-D instances split into spatially connected parts (spatial.py,
+    # tools/split_instances_3d.py).  split_voxel: metres > 0, the cell of the voxel grid -- a few point spacings, e.g. 0.1;
+    # untuned, and required by the tool; split_min_points: a part with fewer points is dropped; split_mode: "split" (every
+    # part becomes an instance) or "largest" (only the largest part of each); split_output_dir: where the tool saves
+    # <cls>/<scene>.pth
+    split_voxel=None, split_min_points=1, split_mode="split", split_output_dir=None,
 )
 
 

@@ -895,6 +895,75 @@ int bff_diag_sweep_lines_u16(const double *xyz, int64_t n_points, int64_t n_pad,
  * -- a gather with a known number of distinct cache lines, to calibrate the FETCH_SIZE counter (scripts/diag_membw.py). */
 int bff_diag_gather(const float *src, int64_t n_lanes, int64_t stride, float *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 3-D instances split into spatially connected parts (no counterpart in the reference).
+ * The definition is connectivity on a voxel grid: a pure function of the inputs, independent of point order, thread
+ * schedule and run.
+ *
+ * Inputs: points float64 [N][stride >= 3] in the caller's point order; a cell size c > 0, finite, in metres; rows
+ * u64 [K][nw], nw >= ceil(N / 64), whose bits at positions >= N are ignored whatever they hold.
+ *
+ * Grid (class independent, built once per scene).  A point is finite when all three coordinates are.  lo[a] = the minimum
+ * of coordinate a over the finite points; q[p][a] = floor((x[p][a] - lo[a]) / c) in float64 (IEEE subtraction, IEEE
+ * division, floor: NumPy's np.floor((xyz - lo) / c), also where a coordinate sits exactly on a cell boundary).
+ * Limit: q < 2^21 on every axis, else BFF_E_LIMIT.  key[p] = q0 + (q1 << 21) + (q2 << 42); keys[V] = the distinct keys
+ * of the finite points, ascending; vox[p] = the rank of key[p] in keys, -1 for a non-finite point (it belongs to no cell
+ * and appears in no output row); nbr[V][13] = for each cell the ranks of its 13 forward neighbours, the offsets
+ * (d2, d1, d0) in {-1, 0, 1}^3 lexicographically greater than (0, 0, 0), in that order, -1 where the cell is empty or
+ * would lie outside [0, 2^21) on an axis (the axis is tested, the key never wraps).
+ *
+ * Components of row k.  Its occupied cells are those holding at least one point of the row.  Two occupied cells are
+ * linked when they differ by at most 1 on every axis (26-adjacency, corner contact included); a component is a class of
+ * the transitive closure, its point count the number of the row's points in its cells, its anchor its smallest cell
+ * rank.  Rows are independent: a cell shared by two rows links nothing between them.
+ *
+ * Output for min_points >= 1: every component with at least min_points points becomes an output row ("split"), ordered
+ * by parent row ascending, point count descending, anchor ascending; or per parent row only the first of that order
+ * ("largest").  The choice and the order are the host's (spatial.split_rows); the entry points below are the steps.
+ *
+ * Elements: the T occupied (row, cell) pairs, numbered in (row, cell) order:
+ *   e = elem_offs[k] + prefix[k][v >> 6] + popcount(occ[k][v >> 6] below bit (v & 63)).
+ * Limits: N, V < 2^31; K * ceil(V / 64) * 64 < 2^31 (so T < 2^31).  Zero sizes return 0 without a launch. */
+
+/* box: u64 [6], min x, y, z then max x, y, z over the finite points as order-preserving integers (b = the double's bits;
+ * b >> 63 ? ~b : b | 1 << 63); without a finite point the minima stay all ones. */
+int bff_voxel_bounds(const double *points, int64_t n_points, int64_t stride, uint64_t *box, void *stream);
+/* key: i64 [N], the cell key of every finite point, 2^63 - 1 for the others.  lo_host, hi_host: the box as doubles
+ * (HOST pointers, 3 each); floor((hi - lo) / cell) >= 2^21 on an axis is BFF_E_LIMIT. */
+int bff_voxel_keys(const double *points, int64_t n_points, int64_t stride, const double *lo_host, const double *hi_host,
+                   double cell, int64_t *key, void *stream);
+/* sorted_keys: `key` ascending (bff_argsort_i64 with 63 key bits).  head: i32 [N], 1 where a cell's first key stands. */
+int bff_voxel_heads(const int64_t *sorted_keys, int64_t n_points, int32_t *head, void *stream);
+/* order: the argsort (position i of sorted_keys holds point order[i]); heads_incl: i64 [N], the inclusive prefix sum of
+ * head; n_voxels = its last entry.  Writes vox i32 [N] and keys i64 [V]. */
+int bff_voxel_ranks(const int64_t *sorted_keys, const int32_t *order, const int64_t *heads_incl, int64_t n_points,
+                    int64_t n_voxels, int32_t *vox, int64_t *keys, void *stream);
+/* nbr: i32 [V][13]. */
+int bff_voxel_neighbours(const int64_t *keys, int64_t n_voxels, int32_t *nbr, void *stream);
+
+/* occ: u64 [K][vw], vw = ceil(V / 64), cleared here: bit v of row k = the row holds a point of cell v.  prefix: i32
+ * [K][vw], the row's set bits below each word; row_total: i32 [K], the row's set bits.  The caller turns row_total into
+ * elem_offs i32 [K + 1] (exclusive prefix sum; elem_offs[K] = T). */
+int bff_split_occupancy(const uint64_t *rows, int32_t n_rows, int64_t nw, int64_t n_points, const int32_t *vox,
+                        int64_t n_voxels, uint64_t *occ, int32_t *prefix, int32_t *row_total, void *stream);
+/* parent: i32 [T].  Afterwards parent[e] is the smallest element of e's component (the anchor's element), whatever the
+ * interleaving of the compare-and-swap unions was. */
+int bff_split_union(const uint64_t *occ, const int32_t *prefix, const int32_t *elem_offs, int32_t n_rows,
+                    int64_t n_voxels, const int32_t *nbr, int32_t n_elems, int32_t *parent, void *stream);
+/* count: i32 [T], at a root the component's points (0 elsewhere).  kept: i32 [1 + T][2]: kept[0][0] = the number of
+ * roots with count >= min_points, kept[1 + i] = (root element, points) of the i-th in an order that depends on the run
+ * (the host sorts them). */
+int bff_split_count(const uint64_t *rows, int32_t n_rows, int64_t nw, int64_t n_points, const int32_t *vox,
+                    int64_t n_voxels, const uint64_t *occ, const int32_t *prefix, const int32_t *elem_offs,
+                    const int32_t *parent, int32_t n_elems, int32_t min_points, int32_t *count, int32_t *kept,
+                    void *stream);
+/* table: i32 [T], root element -> output row in [0, n_out) or -1.  out: u64 [n_out][nw], cleared here; every point of a
+ * parent row lands in at most one output row. */
+int bff_split_emit(const uint64_t *rows, int32_t n_rows, int64_t nw, int64_t n_points, const int32_t *vox,
+                   int64_t n_voxels, const uint64_t *occ, const int32_t *prefix, const int32_t *elem_offs,
+                   const int32_t *parent, int32_t n_elems, const int32_t *table, int32_t n_out, uint64_t *out,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif
