@@ -96,6 +96,7 @@ SIGNATURES = {
 }
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
          "bff_masks2d_tile_pixels": (c_int32, []), "bff_label_runs_tile_pixels": (c_int32, []), "bff_mask_lookup_rows": (c_int32, [c_int32, c_int32, c_int64]),
+         "bff_cosine_gemm_path": (c_int32, [c_int32, c_int32, c_int32]),
          "bff_chunk_mask_words": (c_int32, [c_int64]), "bff_label_plane_stride": (c_int64, [c_int64]), "bff_resolve_overlaps_max_rows": (c_int32, []),
          "bff_point_tile_size": (c_int32, []), "bff_sweep_frames_per_block": (c_int32, [c_int64, c_int32]), "bff_mesh_lane_box": (c_int32, []), "bff_splat_lane_box": (c_int32, []), "bff_depth_tiled_texels": (c_int64, [c_int32, c_int32]), "bff_merge_scratch_words": (c_int64, [c_int32]), "bff_merge_uses_chunk_bound": (c_int32, [c_int64]),
          "bff_profile_next_merge": (c_int32, [_P, _P]), "bff_group_slice_cap": (c_int32, [c_int32, c_int32]),
@@ -980,9 +981,20 @@ def depth_from_u16(raw, height, width, taps=None, depth_scale=1000.0):
     return out
 
 
+GEMM_PATHS = ("small", "rows", "tile64", "bank768x2", "bank768x4", "bank512")
+
+
+def cosine_gemm_path(na, nb, dim):
+    """The kernel cosine_gemm_f16 / normalized_gemm_f16 launch for this shape in this process: an index into GEMM_PATHS,
+    or -1 where they refuse or return early (bff_cosine_gemm_path; BFF_GEMM_BANK, BFF_GEMM_STAGE are read once)."""
+    return int(load().bff_cosine_gemm_path(na, nb, dim))
+
+
 def cosine_gemm_f16(a, b):
     if a.dtype != torch.float16 or b.dtype != torch.float16:
         raise TypeError("cosine_gemm_f16 takes float16 operands")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError("cosine_gemm_f16: embedding widths differ")
     out = torch.empty((a.shape[0], b.shape[0]), dtype=f32, device=a.device)
     call("bff_cosine_gemm_f16", _ptr(a), a.shape[0], _ptr(b), b.shape[0], a.shape[1], _ptr(out))
     return out
@@ -1005,6 +1017,8 @@ def normalized_gemm_f16(a, b):
     """F.normalize(a) @ b.T for float16 rows (SEG:388-393: b = the already normalised text means): float32 [na][nb]."""
     if a.dtype != torch.float16 or b.dtype != torch.float16:
         raise TypeError("normalized_gemm_f16 takes float16 operands")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError("normalized_gemm_f16: embedding widths differ")
     out = torch.empty((a.shape[0], b.shape[0]), dtype=f32, device=a.device)
     call("bff_normalized_gemm_f16", _ptr(a), a.shape[0], _ptr(b), b.shape[0], a.shape[1], _ptr(out))
     return out

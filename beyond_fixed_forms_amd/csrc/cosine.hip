@@ -16,6 +16,13 @@ namespace bff {
 using half8 = __attribute__((ext_vector_type(8))) _Float16;
 using float4v = __attribute__((ext_vector_type(4))) float;
 
+// The squared norm of a row of A that the epilogues take the root of.  The cosine form (norm_b = 1) divides by |a_i| |b_j|
+// as the reference's expression does: a zero row or column gives 0 / 0 = NaN.  The normalised form (norm_b = 0) is
+// F.normalize(a) @ b.T, and F.normalize divides by max(|a_i|, 1e-12) = sqrt(max(|a_i|^2, 1e-24)): a zero row gives 0.0 in
+// every column (no other row of halves has a norm below 6e-8).  Clamped once per lane, before the rows' values are
+// shuffled to the lanes that divide; a select, not a max against 0 or 1e-24: that form cost the bank kernel 6 % at config 5.
+__device__ __forceinline__ float row_sq(float sq, int norm_b) { return norm_b ? sq : fmaxf(sq, 1e-24f); }
+
 __global__ __launch_bounds__(256) void cosine_gemm_f16_kernel(const _Float16 *__restrict__ a, int na,
                                                                const _Float16 *__restrict__ b, int nb, int dim,
                                                                float *__restrict__ out, int norm_b)
@@ -64,6 +71,7 @@ __global__ __launch_bounds__(256) void cosine_gemm_f16_kernel(const _Float16 *__
     // the four k-quarters of a row live in lanes r, r+16, r+32, r+48
     sa += __shfl_xor(sa, 16); sa += __shfl_xor(sa, 32);
     sb += __shfl_xor(sb, 16); sb += __shfl_xor(sb, 32);
+    sa = row_sq(sa, norm_b);
     const float nbj = norm_b ? sqrtf(sb) : 1.0f;              // column j0 + (lane & 15)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -152,7 +160,7 @@ __global__ __launch_bounds__(256) void cosine_gemm_f16_rows_kernel(const _Float1
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int row = kq * 4 + q;                    // C/D map: col = lane & 15, row = 4*(lane>>4) + q
-                const float nai = sqrtf(red_sa[0][row] + red_sa[1][row] + red_sa[2][row] + red_sa[3][row]);
+                const float nai = sqrtf(row_sq(red_sa[0][row] + red_sa[1][row] + red_sa[2][row] + red_sa[3][row], norm_b));
                 const int i = i0 + row, j = (c0 + t) * 16 + r;
                 if (i < na && j < nb) out[(int64_t)i * nb + j] = sum[q] / (nai * nbj);
             }
@@ -253,6 +261,7 @@ __global__ __launch_bounds__(256) void cosine_gemm_f16_tile64_kernel(const _Floa
         // squared norms: rows live in lanes r, r+16, r+32, r+48 of their own wave; a column's kParts pieces are
         // neighbouring threads of one slot
         sa += __shfl_xor(sa, 16); sa += __shfl_xor(sa, 32);
+        sa = row_sq(sa, norm_b);
 #pragma unroll
         for (int q = 0; q < kSlots; ++q) {
             float v = sq[q];
@@ -368,6 +377,7 @@ __global__ __launch_bounds__(1024) void cosine_gemm_f16_bank_kernel(const _Float
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, fb[st], acc, 0, 0, 0);
             }
             sa += __shfl_xor(sa, 16); sa += __shfl_xor(sa, 32);       // the four k-quarters of a row: lanes r, r+16, r+32, r+48
+            sa = row_sq(sa, norm_b);
             const int i0 = (t0 + tl * (int)gridDim.x) * 16;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -430,6 +440,27 @@ static bool bank_kernel_on()
     return on;
 }
 
+static int bank_stage()
+{
+    static const int stage = [] { const char *e = getenv("BFF_GEMM_STAGE"); return e ? atoi(e) : 2; }();
+    return stage;
+}
+
+// The one place that decides which kernel a shape takes (include/bff_hip.h: bff_cosine_gemm_path).
+enum { kPathNone = -1, kPathSmall = 0, kPathRows = 1, kPathTile64 = 2, kPathBank768x2 = 3, kPathBank768x4 = 4, kPathBank512 = 5 };
+static int cosine_gemm_path(int32_t na, int32_t nb, int32_t dim)
+{
+    if (na <= 0 || nb <= 0 || dim <= 0 || dim % 32 != 0) return kPathNone;
+    if (nb <= 64) return kPathSmall;
+    if (na < 2048) return kPathRows;                           // wide bank: A read once, k split over the block's waves
+    // many rows against a bank of <= 256 columns: the bank stays in registers, A streams through LDS once
+    if (nb <= 256 && (dim == 768 || dim == 512) && bank_kernel_on())
+        return dim == 512 ? kPathBank512 : bank_stage() == 2 ? kPathBank768x2 : kPathBank768x4;
+    return kPathTile64;                                        // many rows, wide bank: the bank's k-slices through LDS
+}
+
+extern "C" int bff_cosine_gemm_path(int32_t na, int32_t nb, int32_t dim) { return cosine_gemm_path(na, nb, dim); }
+
 static int launch_cosine_gemm(const void *a, int32_t na, const void *b, int32_t nb, int32_t dim, float *cos, int norm_b,
                               void *stream, const char *what)
 {
@@ -437,8 +468,12 @@ static int launch_cosine_gemm(const void *a, int32_t na, const void *b, int32_t 
     BFF_REQUIRE(dim % 32 == 0, "%s: dim must be a multiple of 32", what);
     if (na == 0 || nb == 0) return BFF_OK;
     BFF_REQUIRE(a && b && cos, "%s: null pointer", what);
-    if (nb > 64 && nb <= 256 && na >= 2048 && (dim == 768 || dim == 512) && bank_kernel_on()) {
-        // many rows against a bank of <= 256 columns: the bank stays in registers, A streams through LDS once
+    const _Float16 *ha = (const _Float16 *)a, *hb = (const _Float16 *)b;
+    const int path = cosine_gemm_path(na, nb, dim);
+    switch (path) {
+    case kPathBank768x2:
+    case kPathBank768x4:
+    case kPathBank512: {
         const int n_ct = (int)ceil_div(nb, 16), n_tiles = (int)ceil_div(na, 16);
         const size_t lds = sizeof(_Float16) * (size_t)kBankTiles * 16 * kAPitch;
         static bool attr_set = false;
@@ -457,30 +492,28 @@ static int launch_cosine_gemm(const void *a, int32_t na, const void *b, int32_t 
             return n;
         }();
         const int grid = n_tiles < cus ? n_tiles : cus;
-        static const int stage = [] { const char *e = getenv("BFF_GEMM_STAGE"); return e ? atoi(e) : 2; }();
-        if (dim == 768 && stage == 2)
-            cosine_gemm_f16_bank_kernel<768, 2><<<grid, 64 * n_ct, lds, as_stream(stream)>>>((const _Float16 *)a, na, (const _Float16 *)b,
-                                                                                          nb, cos, norm_b, n_tiles);
-        else if (dim == 768)
-            cosine_gemm_f16_bank_kernel<768, 4><<<grid, 64 * n_ct, lds, as_stream(stream)>>>((const _Float16 *)a, na, (const _Float16 *)b,
-                                                                                          nb, cos, norm_b, n_tiles);
+        if (path == kPathBank768x2)
+            cosine_gemm_f16_bank_kernel<768, 2><<<grid, 64 * n_ct, lds, as_stream(stream)>>>(ha, na, hb, nb, cos, norm_b, n_tiles);
+        else if (path == kPathBank768x4)
+            cosine_gemm_f16_bank_kernel<768, 4><<<grid, 64 * n_ct, lds, as_stream(stream)>>>(ha, na, hb, nb, cos, norm_b, n_tiles);
         else
-            cosine_gemm_f16_bank_kernel<512, 4><<<grid, 64 * n_ct, lds, as_stream(stream)>>>((const _Float16 *)a, na, (const _Float16 *)b,
-                                                                                          nb, cos, norm_b, n_tiles);
-        return launched(what);
+            cosine_gemm_f16_bank_kernel<512, 4><<<grid, 64 * n_ct, lds, as_stream(stream)>>>(ha, na, hb, nb, cos, norm_b, n_tiles);
+        break;
     }
-    if (nb > 64 && na >= 2048) {                               // many rows, wide bank: the bank's k-slices through LDS
-        cosine_gemm_f16_tile64_kernel<<<(unsigned)ceil_div(na, 64), 256, 0, as_stream(stream)>>>(
-            (const _Float16 *)a, na, (const _Float16 *)b, nb, dim, cos, norm_b);
-        return launched(what);
+    case kPathTile64:
+        cosine_gemm_f16_tile64_kernel<<<(unsigned)ceil_div(na, 64), 256, 0, as_stream(stream)>>>(ha, na, hb, nb, dim, cos, norm_b);
+        break;
+    case kPathRows:
+        cosine_gemm_f16_rows_kernel<<<(unsigned)ceil_div(na, 16), 256, 0, as_stream(stream)>>>(ha, na, hb, nb, dim, cos, norm_b);
+        break;
+    case kPathSmall: {
+        dim3 grid((unsigned)ceil_div(ceil_div(nb, 16), 4), (unsigned)ceil_div(na, 16));
+        cosine_gemm_f16_kernel<<<grid, 256, 0, as_stream(stream)>>>(ha, na, hb, nb, dim, cos, norm_b);
+        break;
     }
-    if (nb > 64) {                                             // wide bank: A read once, k split over the block's waves
-        cosine_gemm_f16_rows_kernel<<<(unsigned)ceil_div(na, 16), 256, 0, as_stream(stream)>>>(
-            (const _Float16 *)a, na, (const _Float16 *)b, nb, dim, cos, norm_b);
-        return launched(what);
+    default:
+        return fail(BFF_E_ARG, "%s: no kernel for %d x %d x %d", what, na, nb, dim);
     }
-    dim3 grid((unsigned)ceil_div(ceil_div(nb, 16), 4), (unsigned)ceil_div(na, 16));
-    cosine_gemm_f16_kernel<<<grid, 256, 0, as_stream(stream)>>>((const _Float16 *)a, na, (const _Float16 *)b, nb, dim, cos, norm_b);
     return launched(what);
 }
 

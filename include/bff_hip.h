@@ -672,13 +672,23 @@ int bff_argsort_i64(const int64_t *keys, int64_t *keys_scratch, int32_t *order_o
  * a21/a24 -- cosine similarity GEMM on the matrix cores (MFMA f16 -> f32).
  *   cos[i][j] = <a_i, b_j> / (||a_i|| * ||b_j||), float32 accumulate and normalisation
  * (compute_clip_similarity R:93-115; bbox_filter SEG:388-393).  a: f16 [na][dim], b: f16 [nb][dim],
- * dim % 32 == 0, cos: float32 [na][nb]. */
+ * dim % 32 == 0, cos: float32 [na][nb].  A zero row of a gives NaN across its row of cos and a zero row of b NaN down
+ * its column (0 / 0, as the reference's expression dot / (|a| |b|) does). */
 int bff_cosine_gemm_f16(const void *a, int32_t na, const void *b, int32_t nb, int32_t dim,
                         float *cos, void *stream);
 /* a24 -- the box filter's product  F.normalize(box_emb) @ text.T  (SEG:388-393): rows of a are normalised, rows of b
- * are taken as they are (the reference normalises the text mean beforehand, SEG:336).  Same kernels, same limits. */
+ * are taken as they are (the reference normalises the text mean beforehand, SEG:336).  Same kernels, same limits.
+ * F.normalize divides by max(|a_i|, 1e-12), so a zero row of a gives 0.0 across its row of sim (never NaN); a zero row
+ * of b is not normalised at all and gives 0.0 down its column. */
 int bff_normalized_gemm_f16(const void *a, int32_t na, const void *b, int32_t nb, int32_t dim,
                             float *sim, void *stream);
+/* Host only, launches nothing: the kernel the two entry points above launch for this shape in this process --
+ * 0 small (one wave per 16 x 16 tile; nb <= 64), 1 rows (nb > 64, na < 2048), 2 tile64 (nb > 64, na >= 2048, bank through
+ * LDS), 3 / 4 bank-stationary at dim 768 with 2 / 4 staged pieces per thread, 5 bank-stationary at dim 512 (3..5:
+ * na >= 2048, 65 <= nb <= 256) -- or -1 where they refuse the sizes or return without a launch (na or nb 0).  The
+ * environment switches BFF_GEMM_BANK (0: paths 3..5 become 2) and BFF_GEMM_STAGE (other than 2: path 3 becomes 4) are
+ * read once per process.  The launcher switches on this same function. */
+int bff_cosine_gemm_path(int32_t na, int32_t nb, int32_t dim);
 /* a24 -- compute_avg_description_encodings (SEG:324-337): per class c, rows [offs[c], offs[c+1]) of desc (float16 or
  * float32 [n][dim]) are L2-normalised (eps 1e-12 as F.normalize), averaged, and the mean is normalised again;
  * out: same dtype [n_classes][dim]; float32 arithmetic. */
