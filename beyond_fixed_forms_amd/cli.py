@@ -15,7 +15,8 @@ mask_2d file), the class checkpoint by rank 0.
 The third stage, `evaluation_main` (the reference's evaluation/eval/eval_scannet200.py), scores a class's final files
 against the ground truth in one process: AP, AP50, AP25 and the recalls into the class's line of the results file.
 Beside the path: `reproject_main` renders a stage's instances back into the colour frames as 2-D masks, `split_main` cuts
-them into their spatially connected parts; each writes to a directory of its own.
+them into their spatially connected parts, `snap_main` snaps them to the scan's superpoints; each writes to a directory of
+its own.
 """
 from __future__ import annotations
 
@@ -431,6 +432,61 @@ def split_main(argv=None):
             _lib.unpack_rows(parts.rows, grid.n_points).cpu()
         conf = parts.conf.cpu() if torch.is_tensor(parts.conf) else parts.conf
         save_result({"ins": ins, "conf": conf, "final_class": parts.final_class, "parent": parts.parent}, out_dir, cls,
+                    scene_id)
+    return 0
+
+
+def _snap_parser():
+    p = _parser("Beyond-Fixed-Forms 3-D instances snapped to superpoints (MI355X)")
+    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
+                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
+    return p
+
+
+def snap_main(argv=None):
+    """python tools/snap_instances_3d.py --config configs/config.yaml --cls "<class>" [--stage final|mask_3d]
+    For every scene of the class's output directory: the index of superpoint_dir/<scene>.pth built once, every instance
+    snapped to the superpoints it holds snap_ratio of (superpoints.snap_instances) and saved to
+    snap_output_dir/<cls>/<scene>.pth in the stage's own file format, with the surviving rows' input instances under the
+    added key "parent".  Only the cloud's length and the superpoint file are read."""
+    from . import superpoints
+    args = _snap_parser().parse_args(argv)
+    cfg = load_config(args.config)
+    cls = args.cls
+    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
+    if not os.path.isdir(data_path):
+        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
+        return 1
+    out_dir, spp_dir = cfg.get("snap_output_dir"), cfg.get("superpoint_dir")
+    if not out_dir:
+        raise ValueError("snap_output_dir is not set in the config")
+    if not spp_dir:
+        raise ValueError("superpoint_dir is not set in the config")
+    # a bad value stops the run before the first scene
+    superpoints.snap_ratio(cfg), superpoints.snap_mode(cfg), superpoints.snap_min_points(cfg)
+    _lib.load()
+    _host_threads()
+    device = "cuda"
+    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
+        scene_id = name[:-4]
+        print("Working on", scene_id, "class", cls)
+        n_points = int(np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"), mmap_mode="r").shape[0])
+        # the dataset's own file: an ndarray or a tensor of ids (scannet_loader.py:92 accepts both)
+        spp = torch.load(os.path.join(spp_dir, f"{scene_id}.pth"), map_location="cpu", weights_only=False)
+        n_ids = int(spp.numel()) if torch.is_tensor(spp) else int(np.asarray(spp).size)
+        if n_ids != n_points:
+            raise ValueError(f"{scene_id}: a superpoint file of {n_ids} ids for a cloud of {n_points} points")
+        index = superpoints.superpoint_index(spp, device)
+        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+        inst = _saved_instances(result, n_points, device)
+        if inst.rows is None:                                            # the reference's empty forms pass through
+            save_result(result, out_dir, cls, scene_id)
+            continue
+        snapped = superpoints.snap_instances(index, inst, cfg)
+        ins = _lib.rows_to_rle(snapped.rows, n_points) if os.environ.get("BFF_SAVE_RLE") == "1" else \
+            _lib.unpack_rows(snapped.rows, n_points).cpu()
+        conf = snapped.conf.cpu() if torch.is_tensor(snapped.conf) else snapped.conf
+        save_result({"ins": ins, "conf": conf, "final_class": snapped.final_class, "parent": snapped.parent}, out_dir, cls,
                     scene_id)
     return 0
 

@@ -45,6 +45,13 @@ DEFAULTS = dict(
     # part becomes an instance) or "largest" (only the largest part of each); split_output_dir: where the tool saves
     # <cls>/<scene>.pth
     split_voxel=None, split_min_points=1, split_mode="split", split_output_dir=None,
+    # not keys of the reference either: 3-D instances snapped to superpoints (superpoints.py,
+    # tools/snap_instances_3d.py).  superpoint_dir: where the dataset's superpoints/<scene>.pth lie (one integer id per
+    # point), required by the tool; snap_ratio: in (0, 1], the share of a superpoint's points an instance must hold to
+    # take it whole, untuned; snap_mode: "snap" (rows are independent and may overlap) or "exclusive" (a superpoint goes
+    # to the one row that holds most of it); snap_min_points: a snapped instance with fewer points is dropped;
+    # snap_output_dir: where the tool saves <cls>/<scene>.pth
+    superpoint_dir=None, snap_ratio=0.5, snap_mode="snap", snap_min_points=1, snap_output_dir=None,
 )
 
 

@@ -368,3 +368,26 @@ def class_scene(scene: SceneInputs, mask_2d: List[dict]) -> SceneInputs:
     out = copy.copy(scene)
     out.mask_2d = mask_2d
     return out
+
+
+def make_superpoints(scene: SceneInputs, cell: float = 0.25, leak: float = 0.0, seed: int = 0) -> np.ndarray:
+    """A stand-in for a dataset's superpoints/<scene>.pth: one int64 id per point.  A superpoint is the points of one
+    object (`point_object`) inside one voxel cell of `cell` metres; a fraction `leak` of the cells ignores the object id,
+    so that its superpoint straddles the objects meeting there, which real ones sometimes do.  The ids are compacted and
+    then shuffled: neither dense-sorted nor aligned with point order."""
+    if scene.point_object is None:
+        raise ValueError("make_superpoints needs the generator's point_object")
+    if not (cell > 0.0 and np.isfinite(cell)) or not (0.0 <= leak <= 1.0):
+        raise ValueError(f"make_superpoints: cell > 0 and 0 <= leak <= 1 expected, got {cell!r}, {leak!r}")
+    rng = np.random.default_rng(seed)
+    xyz = np.asarray(scene.points, dtype=np.float64)[:, :3]
+    q = np.floor((xyz - xyz.min(0)) / float(cell)).astype(np.int64)
+    cells, of_point = np.unique(q, axis=0, return_inverse=True)
+    of_point = of_point.reshape(-1)
+    obj = np.asarray(scene.point_object, dtype=np.int64).reshape(-1)
+    obj = obj - obj.min() + 1
+    leaky = (rng.random(len(cells)) < leak)[of_point]               # drawn for leak = 0 too: the shuffle below stays the same
+    obj = np.where(leaky, 0, obj)
+    _, dense = np.unique(of_point * (int(obj.max()) + 1) + obj, return_inverse=True)
+    dense = dense.reshape(-1)
+    return rng.permutation(int(dense.max()) + 1).astype(np.int64)[dense]

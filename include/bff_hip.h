@@ -974,6 +974,49 @@ int bff_split_emit(const uint64_t *rows, int32_t n_rows, int64_t nw, int64_t n_p
                    const int32_t *parent, int32_t n_elems, const int32_t *table, int32_t n_out, uint64_t *out,
                    void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 3-D instances snapped to superpoints (the reference only loads superpoint files:
+ * evaluation/dataset/scannet_loader.py:92, read_spp).  Integer arithmetic throughout: a pure function of the inputs,
+ * independent of thread schedule and run.
+ *
+ * Inputs: spp, one integer id per point of the cloud in the caller's point order (arbitrary int64 values: not dense, not
+ * sorted); rows u64 [K][nw], nw >= ceil(N / 64), whose bits at positions >= N are ignored whatever they hold and are
+ * zero in every output; ratio in (0, 1]; a mode.
+ *
+ * Index (class independent, built once per scene).  The distinct ids >= 0, ascending, are the S superpoints.  seg[p] =
+ * the rank of point p's id, -1 for a negative id; size[s] = the number of points of superpoint s; order lists the
+ * points of superpoint s at order[offs[s] .. offs[s + 1]) in ascending point index (a stable sort); free = one bit row
+ * holding the points with seg = -1.  A point with a negative id belongs to no superpoint: its bit passes through every
+ * step unchanged.  The index needs no entry point of its own: ids < 0 -> 2^63 - 1, bff_argsort_i64 with 63 key bits,
+ * bff_voxel_heads, bff_voxel_ranks (seg = its vox, the ids = its keys), a prefix sum for offs, a packed comparison
+ * for free.
+ *
+ * need[s] = max(1, ceil(float64(ratio) * size[s])): product and ceiling in float64, once per (index, ratio), outside
+ * the kernels, which compare integers only (ratio 0.55 and 100 points need 56: 0.55 * 100 = 55.00000000000001).
+ * count[k][s] = the number of points of row k in superpoint s.
+ * Mode "snap": output row k = the union of every superpoint with count[k][s] >= need[s], plus rows[k] & free.  Rows are
+ * independent and may overlap.
+ * Mode "exclusive": among the rows that reach need[s], superpoint s goes to the one with the largest count, a tie to the
+ * smallest row index; that row gets the whole superpoint and no other row any of it.  Free points as in "snap".
+ * After: rows with fewer than min_points >= 1 points are dropped, the others keep their order (the host's:
+ * superpoints.snap_rows).
+ *
+ * Limits: N, S < 2^31; K * S < 2^31, else BFF_E_LIMIT.  Zero sizes return 0 without a launch.  No call allocates or
+ * synchronises. */
+
+/* seg: i32 [N].  count: i32 [K][S], cleared here.  Entries of seg outside [0, S) count nowhere. */
+int bff_spp_count(const uint64_t *rows, int32_t n_rows, int64_t nw, int64_t n_points, const int32_t *seg,
+                  int64_t n_segments, int32_t *count, void *stream);
+/* need: i32 [S].  owner: i32 [S], the row that takes superpoint s in "exclusive" mode, -1 = none reaches need[s]. */
+int bff_spp_owner(const int32_t *count, int32_t n_rows, int64_t n_segments, const int32_t *need, int32_t *owner,
+                  void *stream);
+/* owner: NULL = "snap" (superpoint s goes to every row with count[k][s] >= need[s]), else "exclusive" (to row owner[s]).
+ * order: i32 [N']; offs: i32 [S + 1], ascending, offs[S] = N' = the points with seg >= 0.  out: u64 [K][nw], on entry
+ * rows & free with the bits at positions >= N zero; the chosen superpoints' points are ORed in.  An entry of order
+ * outside [0, 64 * nw) sets nothing. */
+int bff_spp_fill(const int32_t *count, int32_t n_rows, int64_t n_segments, const int32_t *need, const int32_t *owner,
+                 const int32_t *order, const int32_t *offs, uint64_t *out, int64_t nw, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
