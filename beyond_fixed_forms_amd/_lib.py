@@ -384,6 +384,23 @@ def count_viewed(xyz_soa, n_points, inv_pose, cam_intr, depth, depth_index, heig
 RENDER_SCRATCH_TEXELS = 1 << 26     # texels of the renderer's uint32 scratch (256 MB): more frames than fit are rendered in runs
 
 
+def _k9(cam_intr):
+    return ctypes.cast((c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)]), c_void_p)
+
+
+def _render_in_runs(inv_pose, depth_h, depth_w, scratch_texels, run, n_out=1):
+    """The frame runs of a render call -> n_out tensors int16 [F][depth_h][depth_w]: one uint32 scratch of at most
+    scratch_texels texels (None: RENDER_SCRATCH_TEXELS), and run(poses, frames, scratch, *outs) -- pointers, of the run's
+    frames -- for as many frames at a time as the scratch holds (at least one; once with no frames when F = 0)."""
+    f, plane = int(inv_pose.shape[0]), int(depth_h) * int(depth_w)
+    outs = [torch.empty((f, int(depth_h), int(depth_w)), dtype=torch.int16, device=inv_pose.device) for _ in range(n_out)]
+    per = max(1, min(f, (RENDER_SCRATCH_TEXELS if scratch_texels is None else int(scratch_texels)) // max(plane, 1)))
+    scratch = torch.empty(max(per * plane, 1), dtype=i32, device=inv_pose.device)
+    for f0 in range(0, max(f, 1), per):
+        run(_ptr(inv_pose[f0:f0 + per], f64), min(per, f - f0), _ptr(scratch), *[_ptr(o[f0:f0 + per]) for o in outs])
+    return outs
+
+
 def render_depth(xyz_soa, n_points, inv_pose, cam_intr, height, width, depth_h, depth_w, tile_bounds=None,
                  frames_per_block=0, scratch_texels=None, splat_radius=0.0):
     """Depth frames out of the cloud itself (bff_render_depth_u16): every point of `xyz_soa` that projects in bounds and
@@ -397,21 +414,16 @@ def render_depth(xyz_soa, n_points, inv_pose, cam_intr, height, width, depth_h, 
     definition is the header's; anything else is rejected by the library)."""
     splat_radius = float(splat_radius)
     splat = splat_radius != 0.0                                # NaN included: the library rejects it
-    k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
-    f, plane = int(inv_pose.shape[0]), int(depth_h) * int(depth_w)
-    out = torch.empty((f, int(depth_h), int(depth_w)), dtype=torch.int16, device=xyz_soa.device)
-    per = max(1, min(f, (RENDER_SCRATCH_TEXELS if scratch_texels is None else int(scratch_texels)) // max(plane, 1)))
-    scratch = torch.empty(max(per * plane, 1), dtype=i32, device=xyz_soa.device)
-    for f0 in range(0, max(f, 1), per):
-        f1 = min(f, f0 + per)
-        head = (_ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(inv_pose[f0:f1], f64), ctypes.cast(k, c_void_p), f1 - f0,
-                int(height), int(width), int(depth_h), int(depth_w))
-        tail = (int(frames_per_block), _ptr(scratch), _ptr(out[f0:f1]), _ptr(tile_bounds, f64))
+
+    def run(poses, frames, scratch, out):
+        head = (_ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], poses, _k9(cam_intr), frames, int(height), int(width),
+                int(depth_h), int(depth_w))
+        tail = (int(frames_per_block), scratch, out, _ptr(tile_bounds, f64))
         if splat:
             call("bff_render_splat_depth_u16", *head, splat_radius, *tail)
         else:
             call("bff_render_depth_u16", *head, *tail)
-    return out
+    return _render_in_runs(inv_pose, depth_h, depth_w, scratch_texels, run)[0]
 
 
 def render_mesh_depth(vertices_soa, n_vertices, faces, inv_pose, cam_intr, height, width, depth_h, depth_w,
@@ -427,21 +439,16 @@ def render_mesh_depth(vertices_soa, n_vertices, faces, inv_pose, cam_intr, heigh
         raise ValueError("render_mesh_depth: faces must be a contiguous int32 [T][3] tensor")
     near_clip = float(near_clip)
     clip = near_clip != 0.0                                    # NaN included: the library rejects it
-    k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
-    f, plane = int(inv_pose.shape[0]), int(depth_h) * int(depth_w)
-    out = torch.empty((f, int(depth_h), int(depth_w)), dtype=torch.int16, device=vertices_soa.device)
-    per = max(1, min(f, (RENDER_SCRATCH_TEXELS if scratch_texels is None else int(scratch_texels)) // max(plane, 1)))
-    scratch = torch.empty(max(per * plane, 1), dtype=i32, device=vertices_soa.device)
-    for f0 in range(0, max(f, 1), per):
-        f1 = min(f, f0 + per)
-        head = (_ptr(vertices_soa, f64), int(n_vertices), vertices_soa.shape[1], _ptr(faces), int(faces.shape[0]),
-                _ptr(inv_pose[f0:f1], f64), ctypes.cast(k, c_void_p), f1 - f0, int(height), int(width), int(depth_h), int(depth_w))
-        tail = (int(frames_per_block), _ptr(scratch), _ptr(out[f0:f1]))
+
+    def run(poses, frames, scratch, out):
+        head = (_ptr(vertices_soa, f64), int(n_vertices), vertices_soa.shape[1], _ptr(faces), int(faces.shape[0]), poses,
+                _k9(cam_intr), frames, int(height), int(width), int(depth_h), int(depth_w))
+        tail = (int(frames_per_block), scratch, out)
         if clip:
             call("bff_render_mesh_depth_clip_u16", *head, near_clip, *tail)
         else:
             call("bff_render_mesh_depth_u16", *head, *tail)
-    return out
+    return _render_in_runs(inv_pose, depth_h, depth_w, scratch_texels, run)[0]
 
 
 MAX_POINT_LABEL = 65534            # labels of bff_render_labels_u16 (65535 << 16 | 65535 is its empty key)
@@ -467,20 +474,12 @@ def render_labels(xyz_soa, n_points, lab, inv_pose, cam_intr, height, width, dep
     arguments byte for byte.  Scratch cap and frame runs are render_depth's."""
     if lab.shape[0] != n_points:
         raise ValueError(f"render_labels: {lab.shape[0]} labels for {n_points} points")
-    k = (c_double * 9)(*[float(v) for v in cam_intr.reshape(-1)])
-    f, plane = int(inv_pose.shape[0]), int(depth_h) * int(depth_w)
-    dev = xyz_soa.device
-    labels = torch.empty((f, int(depth_h), int(depth_w)), dtype=torch.int16, device=dev)
-    depth = torch.empty_like(labels) if want_depth else None
-    per = max(1, min(f, (RENDER_SCRATCH_TEXELS if scratch_texels is None else int(scratch_texels)) // max(plane, 1)))
-    scratch = torch.empty(max(per * plane, 1), dtype=i32, device=dev)
-    for f0 in range(0, max(f, 1), per):
-        f1 = min(f, f0 + per)
+
+    def run(poses, frames, scratch, labels, depth=None):
         call("bff_render_labels_u16", _ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(lab, torch.int16) if n_points else None,
-             _ptr(inv_pose[f0:f1], f64), ctypes.cast(k, c_void_p), f1 - f0, int(height), int(width), int(depth_h), int(depth_w),
-             float(splat_radius), int(frames_per_block), _ptr(scratch), _ptr(labels[f0:f1]),
-             None if depth is None else _ptr(depth[f0:f1]), _ptr(tile_bounds, f64))
-    return labels, depth
+             poses, _k9(cam_intr), frames, int(height), int(width), int(depth_h), int(depth_w), float(splat_radius),
+             int(frames_per_block), scratch, labels, depth, _ptr(tile_bounds, f64))
+    return tuple((_render_in_runs(inv_pose, depth_h, depth_w, scratch_texels, run, n_out=2 if want_depth else 1) + [None])[:2])
 
 
 def label_runs_count(labels, height, width, n_labels):

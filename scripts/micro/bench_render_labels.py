@@ -1,4 +1,4 @@
-"""The label z-buffer (bff_render_labels_u16) beside the depth renderer it is a sibling of, and the label image -> run
+"""The label z-buffer (bff_render_labels_u16) beside the depth renderer of the same kernel, and the label image -> run
 tables step, on a config-2-sized scene: bench_splat_depth.py's cloud (the generator's room and cuboids tessellated to
 about 200 k points), 300 frames, 968 x 1296, strides 2, 4 and 8, radius 0.02 m; the cloud is cut into slabs along x and
 every second slab is an instance (40 by default, about half the points stay background).  The legs,
