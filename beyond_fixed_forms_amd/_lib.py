@@ -100,6 +100,7 @@ SIGNATURES = {
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
          "bff_masks2d_tile_pixels": (c_int32, []), "bff_label_runs_tile_pixels": (c_int32, []), "bff_mask_lookup_rows": (c_int32, [c_int32, c_int32, c_int64]),
          "bff_cosine_gemm_path": (c_int32, [c_int32, c_int32, c_int32]),
+         "bff_cross_popcount_slices": (c_int32, [c_int32, c_int32, c_int64]),
          "bff_chunk_mask_words": (c_int32, [c_int64]), "bff_label_plane_stride": (c_int64, [c_int64]), "bff_resolve_overlaps_max_rows": (c_int32, []),
          "bff_point_tile_size": (c_int32, []), "bff_sweep_frames_per_block": (c_int32, [c_int64, c_int32]), "bff_mesh_lane_box": (c_int32, []), "bff_splat_lane_box": (c_int32, []), "bff_depth_tiled_texels": (c_int64, [c_int32, c_int32]), "bff_merge_scratch_words": (c_int64, [c_int32]), "bff_merge_uses_chunk_bound": (c_int32, [c_int64]),
          "bff_profile_next_merge": (c_int32, [_P, _P]), "bff_group_slice_cap": (c_int32, [c_int32, c_int32]),

@@ -65,7 +65,11 @@ __global__ __launch_bounds__(256) void or_reduce_groups_kernel(const uint64_t *_
     }
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int lo = offs[g] + blockIdx.z * kOrSplit, hi = min(offs[g + 1], lo + kOrSplit);
-    if (lo >= hi) return;                                          // block-uniform
+    if (lo >= hi) {                                                // block-uniform
+        // one z slice: nothing zeroed the output, so an empty group's row is stored here (with more slices the memset did it)
+        if (gridDim.z == 1 && w < nw) out[(int64_t)g * nw + w] = 0;
+        return;
+    }
     uint64_t v = 0;
     if (cmask) {                                                   // long rows: see or_reduce_grouped_kernel
         if (threadIdx.x < hi - lo) {

@@ -137,6 +137,7 @@ extern "C" int bff_unpack_rows(const uint64_t *rows, int32_t n_rows, int64_t nw,
     BFF_REQUIRE(n_rows >= 0 && n_points >= 0 && nw == ceil_div(n_points, 64), "bff_unpack_rows: bad sizes");
     if (n_rows == 0 || n_points == 0) return BFF_OK;
     BFF_REQUIRE(rows && dense, "bff_unpack_rows: null pointer");
+    BFF_LIMIT(n_rows <= 65535, "bff_unpack_rows: too many rows");
     dim3 grid((unsigned)ceil_div(ceil_div(n_points, 8), 256), (unsigned)n_rows);
     unpack_rows_kernel<<<grid, 256, 0, as_stream(stream)>>>(rows, nw, n_points, dense);
     return launched("bff_unpack_rows");
@@ -148,6 +149,7 @@ extern "C" int bff_pack_rows(const uint8_t *dense, int32_t n_rows, int64_t n_poi
     BFF_REQUIRE(n_rows >= 0 && n_points >= 0 && nw == ceil_div(n_points, 64), "bff_pack_rows: bad sizes");
     if (n_rows == 0 || n_points == 0) return BFF_OK;
     BFF_REQUIRE(rows && dense, "bff_pack_rows: null pointer");
+    BFF_LIMIT(n_rows <= 65535, "bff_pack_rows: too many rows");
     dim3 grid((unsigned)ceil_div(nw * 64, 256), (unsigned)n_rows);
     pack_rows_kernel<<<grid, 256, 0, as_stream(stream)>>>(dense, n_points, nw, rows);
     return launched("bff_pack_rows");
@@ -159,6 +161,7 @@ extern "C" int bff_rle_to_rows(const int32_t *run_start, const int32_t *run_end,
     BFF_REQUIRE(n_rows >= 0 && n_points >= 0 && nw == ceil_div(n_points, 64), "bff_rle_to_rows: bad sizes");
     if (n_rows == 0 || nw == 0) return BFF_OK;
     BFF_REQUIRE(row_run_offs && rows, "bff_rle_to_rows: null pointer");   // run arrays may be empty (NULL)
+    BFF_LIMIT(n_rows <= 65535, "bff_rle_to_rows: too many rows");
     dim3 grid((unsigned)ceil_div(nw, 256), (unsigned)n_rows);
     rle_to_rows_kernel<<<grid, 256, 0, as_stream(stream)>>>(run_start, run_end, row_run_offs, n_points, nw, rows);
     return launched("bff_rle_to_rows");

@@ -205,9 +205,34 @@ extern "C" int bff_popcount_rows(const uint64_t *rows, const int32_t *idx, int32
 {
     BFF_REQUIRE(n_rows >= 0 && nw >= 0, "bff_popcount_rows: bad sizes");
     if (n_rows == 0) return BFF_OK;
-    BFF_REQUIRE(rows && area, "bff_popcount_rows: null pointer");
+    BFF_REQUIRE(area && (rows || nw == 0), "bff_popcount_rows: null pointer");
+    if (nw == 0) {                                      // zero-width rows (rows may be NULL): every count is 0
+        hipError_t e = hipMemsetAsync(area, 0, sizeof(int32_t) * (size_t)n_rows, as_stream(stream));
+        if (e != hipSuccess) return fail((int)e, "bff_popcount_rows: memset: %s", hipGetErrorString(e));
+        return BFF_OK;
+    }
     popcount_rows_kernel<<<n_rows, 256, 0, as_stream(stream)>>>(rows, idx, nw, area);
     return launched("bff_popcount_rows");
+}
+
+// The z extent of bff_cross_popcount's launch and the words each slice owns: the one statement of that choice
+// (bff_cross_popcount_slices answers with it, the launch is sized by it).  0 slices: nothing to launch.
+static int64_t cross_popcount_split(int64_t na, int64_t nb, int64_t nw, int64_t *k_split)
+{
+    *k_split = nw;                                      // words per block along z
+    if (na <= 0 || nb <= 0 || nw <= 0) return 0;
+    const int64_t tiles = ceil_div(nb, kT) * ceil_div(na, kT);
+    if (tiles < 512) {                                  // few tiles: split the words so >= ~512 blocks run
+        *k_split = ceil_div(ceil_div(nw * tiles, 512), kKW) * kKW;
+        if (*k_split < 2 * kKW) *k_split = 2 * kKW;
+    }
+    return ceil_div(nw, *k_split);
+}
+
+extern "C" int bff_cross_popcount_slices(int32_t na, int32_t nb, int64_t nw)
+{
+    int64_t k_split;
+    return (int)cross_popcount_split(na, nb, nw, &k_split);
 }
 
 extern "C" int bff_cross_popcount(const uint64_t *a, const int32_t *ia, int32_t na, const uint64_t *b,
@@ -215,17 +240,13 @@ extern "C" int bff_cross_popcount(const uint64_t *a, const int32_t *ia, int32_t 
 {
     BFF_REQUIRE(na >= 0 && nb >= 0 && nw >= 0, "bff_cross_popcount: bad sizes");
     if (na == 0 || nb == 0) return BFF_OK;
-    BFF_REQUIRE(a && b && inter, "bff_cross_popcount: null pointer");
-    const int64_t tiles = ceil_div(nb, kT) * ceil_div(na, kT);
-    int64_t k_split = nw;                               // words per block along z
-    if (tiles < 512) {                                  // few tiles: split the words so >= ~512 blocks run
-        k_split = ceil_div(ceil_div(nw * tiles, 512), kKW) * kKW;
-        if (k_split < 2 * kKW) k_split = 2 * kKW;
-    }
-    const int64_t nz = ceil_div(nw, k_split);
-    if (nz > 1) {
+    BFF_REQUIRE(inter && ((a && b) || nw == 0), "bff_cross_popcount: null pointer");
+    int64_t k_split;
+    const int64_t nz = cross_popcount_split(na, nb, nw, &k_split);
+    if (nz != 1) {                                      // split words meet through atomics; zero-width rows: all zero
         hipError_t e = hipMemsetAsync(inter, 0, sizeof(int32_t) * (size_t)na * nb, as_stream(stream));
         if (e != hipSuccess) return fail((int)e, "bff_cross_popcount: memset: %s", hipGetErrorString(e));
+        if (nz == 0) return BFF_OK;
     }
     dim3 grid((unsigned)ceil_div(nb, kT), (unsigned)ceil_div(na, kT), (unsigned)nz);
     cross_popcount_kernel<<<grid, 256, 0, as_stream(stream)>>>(a, ia, na, b, ib, nb, nw, k_split, inter, nullptr, 0, 0);
@@ -289,6 +310,7 @@ extern "C" int bff_permute_bits(const uint64_t *rows_in, int32_t n_rows, int64_t
     BFF_REQUIRE(n_rows >= 0 && n_out >= 0 && nw_out == ceil_div(n_out, 64) && nw_in >= 0, "bff_permute_bits: bad sizes");
     if (n_rows == 0 || n_out == 0) return BFF_OK;
     BFF_REQUIRE(rows_in && idx && rows_out, "bff_permute_bits: null pointer");
+    BFF_LIMIT(n_rows <= 65535, "bff_permute_bits: too many rows");
     dim3 grid((unsigned)ceil_div(nw_out * 64, 256), (unsigned)n_rows);
     permute_bits_kernel<<<grid, 256, 0, as_stream(stream)>>>(rows_in, nw_in, idx, n_out, nw_out, rows_out);
     return launched("bff_permute_bits");
@@ -308,6 +330,7 @@ extern "C" int bff_and_rows(uint64_t *rows, int32_t n_rows, int64_t nw, const ui
     BFF_REQUIRE(n_rows >= 0 && nw >= 0, "bff_and_rows: bad sizes");
     if (n_rows == 0 || nw == 0) return BFF_OK;
     BFF_REQUIRE(rows && keep, "bff_and_rows: null pointer");
+    BFF_LIMIT(n_rows <= 65535, "bff_and_rows: too many rows");
     dim3 grid((unsigned)ceil_div(nw, 256), (unsigned)n_rows);
     and_rows_kernel<<<grid, 256, 0, as_stream(stream)>>>(rows, nw, keep);
     return launched("bff_and_rows");
@@ -319,6 +342,7 @@ extern "C" int bff_gather_rows(const uint64_t *rows, const int32_t *idx, int32_t
     BFF_REQUIRE(n_out >= 0 && nw >= 0, "bff_gather_rows: bad sizes");
     if (n_out == 0 || nw == 0) return BFF_OK;
     BFF_REQUIRE(rows && idx && out, "bff_gather_rows: null pointer");
+    BFF_LIMIT(n_out <= 65535, "bff_gather_rows: too many rows");
     dim3 grid((unsigned)ceil_div(nw, 256), (unsigned)n_out);
     gather_rows_kernel<<<grid, 256, 0, as_stream(stream)>>>(rows, idx, nw, out);
     return launched("bff_gather_rows");

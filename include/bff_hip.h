@@ -427,16 +427,27 @@ int bff_event_synchronize(void *event);
  * Bit-row primitives (a8-a13, a16-a20).
  */
 
-/* area[r] = popcount(rows[idx ? idx[r] : r])          (torch.sum(dim=1) at P:161,592,596; R:86-87) */
+/* Row counts that become the y extent of a launch are limited to 65535: bff_pack_rows, bff_unpack_rows, bff_and_rows,
+ * bff_gather_rows (n_out), bff_permute_bits, bff_rle_to_rows, bff_scatter_bits and bff_ids_to_rows (n_values) answer
+ * BFF_E_LIMIT beyond that, before anything is launched or written. */
+
+/* area[r] = popcount(rows[idx ? idx[r] : r])          (torch.sum(dim=1) at P:161,592,596; R:86-87)
+ * nw == 0 (zero-width rows; rows may be NULL then): every area is 0. */
 int bff_popcount_rows(const uint64_t *rows, const int32_t *idx, int32_t n_rows, int64_t nw,
                       int32_t *area, void *stream);
 
 /* inter[i][j] = popcount(a[ia[i]] & b[ib[j]]), int32 [na][nb]: the {0,1} matmuls of
  * calculate_iou_between_stages R:84 and the any-overlap test of solve_overlapping P:289-292.
- * ia / ib may be NULL (identity). */
+ * ia / ib may be NULL (identity).  nw == 0 (zero-width rows; a and b may be NULL then): inter is all zero, nothing
+ * but the clear is issued. */
 int bff_cross_popcount(const uint64_t *a, const int32_t *ia, int32_t na,
                        const uint64_t *b, const int32_t *ib, int32_t nb, int64_t nw,
                        int32_t *inter, void *stream);
+/* The z extent of that launch: the words of a row are split over this many blocks per 64 x 64 tile (fewer than 512
+ * tiles: slices of >= 64 words until ~512 blocks run; else 1).  1 = every entry is stored once; > 1 = partial counts
+ * meet through atomics in a zeroed matrix; 0 = nothing is launched (an empty operand or nw == 0).  Read-only: results
+ * never depend on it; tests ask it to know which path a shape reaches. */
+int bff_cross_popcount_slices(int32_t na, int32_t nb, int64_t nw);
 
 /* Per-row statistics that make the Gram block-sparse: area[r] = popcount(row r); mean_word[r] = mean word
  * index of its set bits (INT32_MAX for an empty row; a sort key that groups rows covering the same part of
@@ -542,7 +553,9 @@ int bff_components_round(const uint64_t *adj, int32_t n_nodes, const int32_t *la
  * also the `.any(dim=0)` merge of R:269).  max_group_size >= the largest group (host knows the groups);
  * it only sizes the launch.  conf / conf_mean (optional, both or neither; dtype as bff_group_conf_mean): the
  * same launch also computes bff_group_conf_mean on extra blocks, so the long sequential sums run beside the OR.
- * chunk_mask (optional, the rows' chunk flags): long rows are read through it. */
+ * chunk_mask (optional, the rows' chunk flags): long rows are read through it.
+ * A group without members (group_offs[g] == group_offs[g+1]) gets an all-zero row, whatever max_group_size is, and
+ * the mean 0 / 0 = NaN. */
 int bff_or_reduce_groups(const uint64_t *rows, int64_t nw, const int32_t *group_offs, const int32_t *members,
                          int32_t n_groups, int32_t max_group_size, uint64_t *out, const void *conf,
                          int32_t conf_dtype, void *conf_mean, const uint64_t *chunk_mask, void *stream);
