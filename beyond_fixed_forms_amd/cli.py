@@ -15,8 +15,9 @@ mask_2d file), the class checkpoint by rank 0.
 The third stage, `evaluation_main` (the reference's evaluation/eval/eval_scannet200.py), scores a class's final files
 against the ground truth in one process: AP, AP50, AP25 and the recalls into the class's line of the results file.
 Beside the path: `reproject_main` renders a stage's instances back into the colour frames as 2-D masks, `split_main` cuts
-them into their spatially connected parts, `snap_main` snaps them to the scan's superpoints; each writes to a directory of
-its own.
+them into their spatially connected parts, `snap_main` snaps them to the scan's superpoints, `subsample_main` writes a
+voxel subsample of every cloud and `lift_main` carries the instances of a run on it back to the full cloud; each writes
+to a directory of its own.
 """
 from __future__ import annotations
 
@@ -488,6 +489,111 @@ def snap_main(argv=None):
         conf = snapped.conf.cpu() if torch.is_tensor(snapped.conf) else snapped.conf
         save_result({"ins": ins, "conf": conf, "final_class": snapped.final_class, "parent": snapped.parent}, out_dir, cls,
                     scene_id)
+    return 0
+
+
+def _subsample_parser():
+    p = argparse.ArgumentParser(description="Beyond-Fixed-Forms voxel subsample of the scene clouds (MI355X)")
+    p.add_argument("--config", type=str, required=True, help="Config")
+    p.add_argument("--scene", type=str, action="append", default=None,
+                   help="A scene id (repeatable); without it every <scene>.npy of scene_npy_dir")
+    return p
+
+
+def subsample_main(argv=None):
+    """python tools/subsample_cloud.py --config configs/config.yaml [--scene <id> ...]
+    For every scene_npy_dir/<scene>.npy (or the named ones): one point of every cell of subsample_voxel metres
+    (lift.subsample), saved as subsample_npy_dir/<scene>.npy -- those rows of the file, all columns, dtype kept -- with
+    the kept indices (int32) in subsample_npy_dir/sample/<scene>.npy.  A second config whose scene_npy_dir names that
+    folder runs the projection stage unchanged on the small clouds."""
+    from . import lift
+    args = _subsample_parser().parse_args(argv)
+    cfg = load_config(args.config)
+    out_dir = cfg.get("subsample_npy_dir")
+    if not out_dir:
+        raise ValueError("subsample_npy_dir is not set in the config")
+    voxel = lift.subsample_voxel(cfg)                                    # a bad value stops the run before the first scene
+    src_dir = cfg.get("scene_npy_dir")
+    if not src_dir or not os.path.isdir(src_dir):
+        print(f"no clouds: scene_npy_dir {src_dir!r} is not a directory", file=sys.stderr)
+        return 1
+    if os.path.abspath(out_dir) == os.path.abspath(src_dir):
+        raise ValueError("subsample_npy_dir is scene_npy_dir itself: the clouds would be overwritten")
+    scenes = args.scene if args.scene else sorted(s[:-4] for s in os.listdir(src_dir) if s.endswith(".npy"))
+    _lib.load()
+    _host_threads()
+    os.makedirs(os.path.join(out_dir, "sample"), exist_ok=True)
+    for scene_id in scenes:
+        points = np.load(os.path.join(src_dir, f"{scene_id}.npy"))
+        sample = lift.subsample(points, voxel, "cuda").cpu().numpy()
+        print("Working on", scene_id, ":", len(sample), "of", points.shape[0], "points")
+        np.save(os.path.join(out_dir, f"{scene_id}.npy"), points[sample])
+        np.save(os.path.join(out_dir, "sample", f"{scene_id}.npy"), sample)
+    return 0
+
+
+def _lift_parser():
+    p = _parser("Beyond-Fixed-Forms 3-D instances lifted from a subsampled cloud to the full cloud (MI355X)")
+    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
+                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
+    return p
+
+
+def _saved_mask_length(result):
+    """The point count the masks of a saved stage file were made for, None for the reference's empty forms."""
+    ins = result["ins"]
+    if isinstance(ins, (list, tuple)):
+        return int(ins[0]["length"]) if len(ins) and isinstance(ins[0], dict) else None
+    ins = torch.as_tensor(ins)
+    return int(ins.shape[1]) if ins.dim() == 2 and ins.shape[0] > 0 and ins.shape[1] > 0 else None
+
+
+def lift_main(argv=None):
+    """python tools/lift_instances_3d.py --config configs/config.yaml --cls "<class>" [--stage final|mask_3d]
+    The config is the small run's.  For every scene of the class's output directory: the search index of the small cloud
+    (scene_npy_dir/<scene>.npy) built once, one search for the points of the full cloud (lift_target_npy_dir/<scene>.npy)
+    within lift_max_dist, every instance lifted (lift.lift_instances) and saved to lift_output_dir/<cls>/<scene>.pth in
+    the stage's own file format, the masks of the full cloud's length.  Only the two clouds are read."""
+    from . import lift
+    args = _lift_parser().parse_args(argv)
+    cfg = load_config(args.config)
+    cls = args.cls
+    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
+    if not os.path.isdir(data_path):
+        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
+        return 1
+    out_dir, target_dir = cfg.get("lift_output_dir"), cfg.get("lift_target_npy_dir")
+    if not out_dir:
+        raise ValueError("lift_output_dir is not set in the config")
+    if not target_dir:
+        raise ValueError("lift_target_npy_dir is not set in the config")
+    radius = lift.lift_max_dist(cfg)                                     # a bad value stops the run before the first scene
+    _lib.load()
+    _host_threads()
+    device = "cuda"
+    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
+        scene_id = name[:-4]
+        print("Working on", scene_id, "class", cls)
+        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+        length = _saved_mask_length(result)
+        if length is None:                                               # the reference's empty forms pass through
+            save_result(result, out_dir, cls, scene_id)
+            continue
+        source = np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"))
+        target = np.load(os.path.join(target_dir, f"{scene_id}.npy"))
+        n_source, n_target = int(source.shape[0]), int(target.shape[0])
+        if length != n_source:
+            raise ValueError(f"{scene_id}: masks of {length} points for a source cloud of {n_source} points")
+        inst = _saved_instances(result, n_source, device)
+        if inst.rows is None:
+            save_result(result, out_dir, cls, scene_id)
+            continue
+        nn = lift.nearest(lift.nearest_index(source, radius, device), target)
+        lifted = lift.lift_instances(nn, inst, n_source, n_target)
+        ins = _lib.rows_to_rle(lifted.rows, n_target) if os.environ.get("BFF_SAVE_RLE") == "1" else \
+            _lib.unpack_rows(lifted.rows, n_target).cpu()
+        conf = lifted.conf.cpu() if torch.is_tensor(lifted.conf) else lifted.conf
+        save_result({"ins": ins, "conf": conf, "final_class": lifted.final_class}, out_dir, cls, scene_id)
     return 0
 
 

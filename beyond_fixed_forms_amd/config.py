@@ -52,6 +52,13 @@ DEFAULTS = dict(
     # to the one row that holds most of it); snap_min_points: a snapped instance with fewer points is dropped;
     # snap_output_dir: where the tool saves <cls>/<scene>.pth
     superpoint_dir=None, snap_ratio=0.5, snap_mode="snap", snap_min_points=1, snap_output_dir=None,
+    # not keys of the reference either: running on a voxel subsample of the cloud and lifting the instances back to the
+    # full cloud by nearest neighbour (lift.py, tools/subsample_cloud.py, tools/lift_instances_3d.py).  subsample_voxel:
+    # metres > 0, the cell one point is kept of, untuned; subsample_npy_dir: where the first tool saves the small
+    # <scene>.npy (and sample/<scene>.npy, the kept indices); lift_max_dist: metres > 0, a point of the full cloud farther
+    # than this from every point of the small one joins no instance, absent = 2 x subsample_voxel; lift_target_npy_dir:
+    # where the full clouds lie; lift_output_dir: where the second tool saves <cls>/<scene>.pth
+    subsample_voxel=None, subsample_npy_dir=None, lift_max_dist=None, lift_target_npy_dir=None, lift_output_dir=None,
 )
 
 

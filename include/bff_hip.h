@@ -1030,6 +1030,52 @@ int bff_spp_owner(const int32_t *count, int32_t n_rows, int64_t n_segments, cons
 int bff_spp_fill(const int32_t *count, int32_t n_rows, int64_t n_segments, const int32_t *need, const int32_t *owner,
                  const int32_t *order, const int32_t *offs, uint64_t *out, int64_t nw, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 3-D instances lifted from a subsampled cloud to the full cloud (no counterpart in the
+ * reference).  A pure function of the inputs, independent of thread schedule and run; tests/lift_ref.py restates it in
+ * NumPy and the results are equal bit for bit.
+ *
+ * Subsample.  grid = the grid above (bff_voxel_*) of the cloud at cell v.  The representative of an occupied cell is the
+ * smallest point index in it; a non-finite point has no cell and is never sampled.  sample: int32 [V], the
+ * representatives in ascending point index, so points[sample] keeps the file's order.  It needs no entry point: a
+ * minimum of the point index per cell rank (vox), then the marked points in order (lift.subsample).
+ *
+ * Nearest source within a radius.  Inputs: source points S float64 [M][>= 3], a radius r > 0, finite, query points Q
+ * float64 [N][>= 3].  The source index is the grid above of S with cell c = r, plus the points of every cell in
+ * ascending point index (order, offs: bff_spp_fill's lists with the cells as superpoints).  The query's cell is
+ * floor((x - lo) / c) per axis in float64, with the grid's lo and bff_voxel_keys' IEEE operations, and is tested on the
+ * doubles before any conversion: a query with a non-finite coordinate has nn = -1, and so has one whose cell lies outside
+ * [-1, 2^21] on some axis.  Candidates: the source points whose cell differs from the query's by at most 1 on every
+ * axis.  d2 = (dx * dx + dy * dy) + dz * dz with dx = q.x - s.x, every operation rounded to float64, no fma.  nn[p] =
+ * the candidate with the smallest d2 among those with d2 <= float64(r) * float64(r), equal d2 to the smallest source
+ * index; -1 without one.  d2[p] = that squared distance, +inf without one.
+ *
+ * Lift.  rows_in u64 [K][nw_in] over the M source points, nw_in >= ceil(M / 64); rows_out u64 [K][ceil(N / 64)].  Bit p
+ * of output row k = bit nn[p] of input row k where 0 <= nn[p] < M, and 0 for any other value of nn[p] (-1, and anything
+ * out of range: the device never follows a bad index).  Input bits at positions >= M are ignored, output bits at
+ * positions >= N are zero.  Two steps: the rows transposed into one column of ceil(K / 64) words per source point, then
+ * one gather of a column per target point (K gathers of a bit per target is the wrong shape at K ~ 100).
+ *
+ * Limits: N, M, V < 2^31; K * ceil(N / 64) < 2^31 and M * ceil(K / 64) < 2^31 words, else BFF_E_LIMIT.  Zero sizes
+ * return 0 without a launch.  No call allocates or synchronises. */
+
+/* src: f64 [n_source][3], the source points that have a cell, in (cell, point index) order; order: i32 [n_source], the
+ * source index of each; offs: i32 [V + 1] into both, offs[V] = n_source; keys: i64 [V], the grid's distinct keys,
+ * ascending.  lo_host: the grid's minimum (HOST pointer, 3 doubles); cell: the grid's cell (= radius by the definition
+ * above).  queries: f64 [n_queries][stride >= 3].  nn: i32 [n_queries]; d2: f64 [n_queries] or NULL.  With n_voxels = 0
+ * every query gets -1. */
+int bff_nn_search(const double *src, const int64_t *keys, const int32_t *offs, const int32_t *order, int64_t n_voxels,
+                  int64_t n_source, const double *lo_host, double cell, double radius, const double *queries,
+                  int64_t n_queries, int64_t stride, int32_t *nn, double *d2, void *stream);
+/* cols: u64 [n_source][ceil(n_rows / 64)] (caller-provided scratch, written whole): bit k of cols[s] = bit s of row k,
+ * the bits of rows >= n_rows zero. */
+int bff_rows_to_columns(const uint64_t *rows_in, int32_t n_rows, int64_t nw_in, int64_t n_source, uint64_t *cols,
+                        void *stream);
+/* cols: what bff_rows_to_columns wrote for the same n_rows and n_source.  nn: i32 [n_target].  rows_out: u64
+ * [n_rows][ceil(n_target / 64)], written whole. */
+int bff_lift_bits(const uint64_t *cols, int64_t n_source, int32_t n_rows, const int32_t *nn, int64_t n_target,
+                  uint64_t *rows_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
