@@ -25,6 +25,8 @@ SIGNATURES = {
     "bff_rle_to_labels": [_P, _P, _P, _P, _I, _L, _I, _P, _P, _P, _P],
     "bff_mask_row_directory": [_P, _P, _P, _I, _I, _I, _P, _P],
     "bff_project_views_lookup": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P],
+    "bff_project_views_cached": [_L, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P],
+    "bff_visibility_table": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _L, _P, _I, _P],
     "bff_masks2d_count": [_P, _I, _L, _P, _P, _P],
     "bff_masks2d_runs": [_P, _I, _L, _P, _P, _P, _P],
     "bff_project_views": [_P, _L, _L, _P, _P, _I, _P, _P, _I, _I, _D, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P],
@@ -109,6 +111,8 @@ PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, [
          "bff_profile_next_merge": (c_int32, [_P, _P]), "bff_group_slice_cap": (c_int32, [c_int32, c_int32]),
          "bff_point_threshold_scratch_words": (c_int64, [c_int64]), "bff_point_threshold_capacity": (c_int32, []), "bff_point_threshold_capacity_set": (c_int32, [c_int32]), "bff_scene_header_words": (c_int32, [c_int32, c_int32]), "bff_scene_struct_bytes": (c_int32, [c_int32]),
          "bff_host_component_csr": (c_int32, [_P, _P, _I, _I, _P, _P, _P, _P]),
+         "bff_visibility_words": (c_int64, [c_int64]), "bff_visibility_builds": (c_int64, []),
+         "bff_visibility_table_bytes": (c_int32, [c_int64, c_int32, c_int64, _P]),
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
@@ -363,6 +367,74 @@ def project_views_lookup(xyz_soa, n_points, inv_pose, cam_intr, depth, depth_ind
          _ptr(view_mask_offs, i32), word_bits, _ptr(frame_mask, i32), _ptr(frame_rowbase, i32), _ptr(frame_nmask, i32),
          _ptr(frame_flags, i32), _ptr(rows, i64), 0 if rows is None else rows.shape[0], (n_points + 63) // 64,
          _ptr(chunk_mask, i64), _ptr(masked_count, i32), _ptr(viewed_count, i32), _ptr(tile_bounds, f64))
+
+
+def _depth_layout(depth, depth_size):
+    """(hs, ws, depth_layout) of resident depth frames as the sweeps' entry points take them."""
+    if depth.dtype == torch.int16 or depth_size is not None:
+        hs, ws = (depth_size if depth_size is not None else depth.shape[1:3])
+        return int(hs), int(ws), 0 if depth_size is None else (2 if depth.dtype == f32 else 1)
+    if depth.dtype != f32:
+        raise TypeError(f"expected float32 depth images, got {depth.dtype}")
+    return 0, 0, -1
+
+
+def visibility_words(n_points):
+    """Words per depth slot of a visibility table (bff_visibility_words)."""
+    return int(load().bff_visibility_words(n_points))
+
+
+def visibility_builds():
+    """Visibility tables built by this process so far (bff_visibility_builds)."""
+    return int(load().bff_visibility_builds())
+
+
+def visibility_table_bytes(n_points, n_slots, n_pixels=0):
+    """(bytes of vis_mask, of vis_off, of vis_pix for n_pixels visible pairs) (bff_visibility_table_bytes)."""
+    out = (c_int64 * 3)()
+    rc = load().bff_visibility_table_bytes(n_points, n_slots, n_pixels, ctypes.cast(out, c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"bff_visibility_table_bytes failed ({rc}): {load().bff_last_error().decode()}")
+    return tuple(int(v) for v in out)
+
+
+def visibility_table(xyz_soa, n_points, slot_inv_pose, cam_intr, depth, height, width, depth_thresh, tile_bounds=None,
+                     depth_size=None, max_bytes=None):
+    """The visibility table of a resident scene (bff_visibility_table), built on the current stream: (vis_mask int64
+    [n_slots][visibility_words], vis_off int32 [n_slots][visibility_words], vis_pix int32 [n_pixels]) for the depth slots
+    `depth` holds, slot s seen with slot_inv_pose[s] (f64 [n_slots][16]).  Waits once, for the number of visible pairs
+    between the offsets and the pixel pass.  max_bytes: None is returned instead of a table larger than that."""
+    dev = xyz_soa.device
+    n_slots = int(slot_inv_pose.shape[0])
+    stride = visibility_words(n_points)
+    hs, ws, layout = _depth_layout(depth, depth_size)
+    if max_bytes is not None and sum(visibility_table_bytes(n_points, n_slots)) > max_bytes:
+        return None
+    mask = torch.empty((n_slots, stride), dtype=i64, device=dev)
+    off = torch.empty((n_slots, stride), dtype=i32, device=dev)
+    total = torch.zeros(1, dtype=i64, device=dev)
+    head = (_ptr(xyz_soa, f64), n_points, xyz_soa.shape[1], _ptr(slot_inv_pose, f64), _k9(cam_intr), n_slots, _ptr(depth),
+            hs, ws, layout, height, width, float(depth_thresh), _ptr(tile_bounds, f64), _ptr(mask, i64), _ptr(off, i32))
+    call("bff_visibility_table", *head, None, 0, _ptr(total, i64), 1)
+    n_pixels = int(total.item())
+    if n_pixels >= 1 << 32 or (max_bytes is not None and sum(visibility_table_bytes(n_points, n_slots, n_pixels)) > max_bytes):
+        return None
+    pix = torch.empty(max(n_pixels, 1), dtype=i32, device=dev)
+    call("bff_visibility_table", *head, _ptr(pix, i32), n_pixels, _ptr(total, i64), 2)
+    return mask, off, pix
+
+
+def project_views_cached(n_points, depth_index, height, width, vis, mask_tab, mask_dir, run_start, run_end, view_mask_offs,
+                         word_bits, frame_mask, frame_rowbase, frame_nmask, frame_flags, rows, masked_count, viewed_count,
+                         chunk_mask=None):
+    """project_views_lookup answered from the scene's visibility table `vis` = (vis_mask, vis_off, vis_pix) of
+    visibility_table: no cloud, poses or depth (bff_project_views_cached)."""
+    call("bff_project_views_cached", n_points, depth_index.shape[0], _ptr(depth_index, i32), height, width,
+         _ptr(vis[0], i64), _ptr(vis[1], i32), _ptr(vis[2], i32), _ptr(mask_tab, i32), _ptr(mask_dir, i32),
+         _ptr(run_start, i32), _ptr(run_end, i32), _ptr(view_mask_offs, i32), word_bits, _ptr(frame_mask, i32),
+         _ptr(frame_rowbase, i32), _ptr(frame_nmask, i32), _ptr(frame_flags, i32), _ptr(rows, i64),
+         0 if rows is None else rows.shape[0], (n_points + 63) // 64, _ptr(chunk_mask, i64), _ptr(masked_count, i32),
+         _ptr(viewed_count, i32))
 
 
 def count_viewed(xyz_soa, n_points, inv_pose, cam_intr, depth, depth_index, height, width, depth_thresh, viewed_count,

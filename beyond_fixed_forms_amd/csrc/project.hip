@@ -44,6 +44,19 @@ struct RawDepth {
     float scale;                // 1000
 };
 
+// The per-scene visibility table (bff_visibility_table): what the sweep's geometry and depth test answer per (depth slot,
+// point), kept from call to call -- the answer depends on the cloud, the poses, the depth frames and the threshold only.
+//   mask  [n_slots][stride]  bit l of word w: point 64 w + l passes the sweep's test in the slot's frame
+//   off   [n_slots][stride]  exclusive prefix of the words' popcounts in (slot, word) order
+//   pix   the visible pairs' pixels, u | v << 16, pair (slot, w, l) at off[slot][w] + popcount(mask & lanes below l)
+// stride = bff_visibility_words(n_points): the words of whole sweep blocks, so that every wave of a sweep finds its four.
+struct VisTable {
+    const uint64_t *mask;
+    const uint32_t *off;
+    const uint32_t *pix;
+    int64_t stride;
+};
+
 // io._axis_taps for one destination index: f = (float)((d + 0.5) * scale - 0.5) (float64 products and differences, each
 // rounded once; no contraction), i0 = floor(f), a = f - i0 in float32; x axis: border columns are copied (a = 0), y axis:
 // the fraction is kept and the two row indices are clamped.
@@ -140,7 +153,9 @@ __device__ __forceinline__ uint32_t wave_reduce_pk_u16(uint32_t v)
 
 // kRows: the frame's masks are not decoded into `maskbits`; a visible point asks the masks' row directory (mask_rows.h)
 // at its pixel instead.  The block's <= kRowsFrames frames keep their mask tables in LDS behind the tap table.
-template <typename WordT, bool kLabels, bool kRaw, bool kRows = false>
+// kVis (with kRows): visibility and pixel of a (point, frame) pair come out of the scene's visibility table; the cloud, the
+// poses, the tap table and the depth frames are not touched, and a frame whose four mask words are zero is skipped.
+template <typename WordT, bool kLabels, bool kRaw, bool kRows = false, bool kVis = false>
 __global__ __launch_bounds__(kBlock) void project_views_kernel(
     const double *__restrict__ xyz, int64_t n_points, int64_t n_pad,
     const double *__restrict__ inv_pose, Intrinsics K, int n_frames, int frames_per_block,
@@ -152,8 +167,9 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
     const int32_t *__restrict__ frame_flags,
     uint64_t *__restrict__ rows, int64_t nw, uint64_t *__restrict__ chunk_mask, int mw,
     int32_t *__restrict__ masked_count, int32_t *__restrict__ viewed_count,
-    const double *__restrict__ tile_bounds, MaskRows mr)
+    const double *__restrict__ tile_bounds, MaskRows mr, VisTable vt)
 {
+    static_assert(!kVis || (kRows && !kRaw && !kLabels), "the cached sweep is the look-up sweep without depth");
     // per wave: [bit][kPPT words] transposition buffer for the wave's sector of the frame's rows
     __shared__ uint64_t stage_all[kBlock / kWave][sizeof(WordT) * 8][kPPT];
     extern __shared__ uint32_t s_taps[];                   // kRaw: the resize's tap table (RawDepth::taps), 12 bytes per
@@ -196,7 +212,8 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
         __syncthreads();
     }
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // kVis: the wave index as a scalar, so that the table's words come in by scalar loads
+    const int tid = threadIdx.x, lane = tid & 63, wave = kVis ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     // Block -> XCD mapping is the plain round-robin of the dispatch order.  Both XCD-aware mappings were measured on
     // config 2 and lost: an eighth of the (spatially sorted) cloud per XCD makes the work per XCD uneven -- frustum
     // culling empties whole regions of a frame and dispatch is in order -- (0.34 -> 0.8 ms); one frame tile per XCD, so
@@ -216,12 +233,15 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
         const int64_t n = (word0 + j) * kWave + lane;
         valid[j] = n < n_points;
         const int64_t m = valid[j] ? n : 0;
-        px[j] = xyz[m];
-        py[j] = xyz[n_pad + m];
-        pz[j] = xyz[2 * n_pad + m];
+        if constexpr (!kVis) {
+            px[j] = xyz[m];
+            py[j] = xyz[n_pad + m];
+            pz[j] = xyz[2 * n_pad + m];
+        }
         mcount[j] = 0;
         vcount[j] = 0;
     }
+    constexpr int kGeo = kVis ? 0 : kPPT;                   // points whose geometry and depth a frame evaluates (kVis: none)
 
     const int f1 = min(n_frames, f0 + frames_per_block);
     const double dW = (double)W, dH = (double)H;
@@ -236,7 +256,7 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
     // 1e-6 and m exceed the float64 rounding of these forms (~1e-11) by orders of magnitude; NaN / inf corner
     // values compare false and keep the frame.  Exact: a skipped frame has no in-bounds point in this wave.
     uint64_t culled = 0;                                   // bit 8 k set: frame f0 + k cannot see this wave's points
-    if (tile_bounds && __ballot(valid[0])) {               // the table has one box per tile that holds points (a wave's
+    if (!kVis && tile_bounds && __ballot(valid[0])) {      // the table has one box per tile that holds points (a wave's
                                                            // first point is lane 0's; asking valid[] costs no register)
         const double *bb = tile_bounds + 6 * (word0 / kPPT);
         const int corner = lane & 7, fk = lane >> 3;
@@ -285,8 +305,34 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
         int pix[kPPT];
         int pu[kPPT];                                       // kRaw: the pixel's column (its row is (pix - pu) / W)
         double cz[kPPT];
+        bool tvis[kPPT] = {};                               // kVis: the table's answer
+        if constexpr (kVis) {
+            const int64_t e0 = (int64_t)depth_index[f] * vt.stride + word0;     // wave-uniform
+            // the four mask words and their offsets in one round trip, then the visible lanes' pixels in a second one
+            uint64_t m[kPPT], any = 0;
+            uint32_t at[kPPT];
 #pragma unroll
-        for (int j = 0; j < kPPT; ++j) {
+            for (int j = 0; j < kPPT; ++j) {
+                m[j] = vt.mask[e0 + j];
+                at[j] = vt.off[e0 + j];
+                any |= m[j];
+            }
+            if (!any) continue;                             // nothing of this wave is visible in the frame
+#pragma unroll
+            for (int j = 0; j < kPPT; ++j) {
+                tvis[j] = (m[j] >> lane) & 1;
+                at[j] += __builtin_amdgcn_mbcnt_hi((uint32_t)(m[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[j], 0u));
+                pu[j] = 0;
+            }
+#pragma unroll
+            for (int j = 0; j < kPPT; ++j)
+                if (tvis[j]) pu[j] = (int)vt.pix[at[j]];
+#pragma unroll
+            for (int j = 0; j < kPPT; ++j)
+                pix[j] = tvis[j] ? (pu[j] >> 16) * W + (pu[j] & 0xffff) : -1;
+        }
+#pragma unroll
+        for (int j = 0; j < kGeo; ++j) {
             // k-ascending fma chains from +0.0: bit-identical to the reference's dgemm (header contract)
             const double cx = fma(P[3], 1.0, fma(P[2], pz[j], fma(P[1], py[j], fma(P[0], px[j], 0.0))));
             const double cy = fma(P[7], 1.0, fma(P[6], pz[j], fma(P[5], py[j], fma(P[4], px[j], 0.0))));
@@ -304,7 +350,7 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
         float ta[kPPT], tb[kPPT];
         uint32_t sbits[kPPT], fbits[kPPT];                 // fbits (kLabels): segments in word form
 #pragma unroll
-        for (int j = 0; j < kPPT; ++j) {
+        for (int j = 0; j < kGeo; ++j) {
             dval[j] = 0.0f;
             sbits[j] = 0xffffffffu;
             fbits[j] = 0xffffffffu;
@@ -389,7 +435,7 @@ __global__ __launch_bounds__(kBlock) void project_views_kernel(
             uint32_t bmin = 0xffffffffu, bmax = 0;         // bounding box of the wave's visible pixels
 #pragma unroll
             for (int j = 0; j < kPPT; ++j) {
-                vis[j] = (pix[j] >= 0) && (dval[j] != 0.0f) && (fabs(cz[j] - (double)dval[j]) < thresh);
+                vis[j] = kVis ? tvis[j] : (pix[j] >= 0) && (dval[j] != 0.0f) && (fabs(cz[j] - (double)dval[j]) < thresh);
                 wv[j] = 0;
                 if (vis[j]) {
                     bmin = pk_min_u16(bmin, (uint32_t)pu[j]);
@@ -579,12 +625,15 @@ __global__ void sweep_lines_kernel(const double *__restrict__ xyz, int64_t n_poi
 // the tile is culled against tile_bounds in groups of 8 frames, the fused sweep's exact test.
 constexpr int kCullGroup = 8;                    // frames one culling pass decides (lane = 8 frame + corner)
 
-template <bool kRaw>
+// kBits: the mask pass of bff_visibility_table.  The frames are the scene's depth slots (frame f reads depth slot f), and
+// instead of counting, the ballot of `visible` over the wave's 64 points is stored per word: vis_mask[f][word].
+template <bool kRaw, bool kBits = false>
 __global__ __launch_bounds__(kBlock) void viewed_count_kernel(
     const double *__restrict__ xyz, int64_t n_points, int64_t n_pad,
     const double *__restrict__ inv_pose, Intrinsics K, int n_frames, int frames_per_block,
     const void *__restrict__ depth, RawDepth raw, const int32_t *__restrict__ depth_index, int H, int W, double thresh,
-    int32_t *__restrict__ viewed_count, const double *__restrict__ tile_bounds)
+    int32_t *__restrict__ viewed_count, const double *__restrict__ tile_bounds,
+    uint64_t *__restrict__ vis_mask = nullptr, int64_t vis_stride = 0)
 {
     extern __shared__ uint32_t s_taps[];
     if (kRaw) {
@@ -651,9 +700,10 @@ __global__ __launch_bounds__(kBlock) void viewed_count_kernel(
         for (int f = g0; f < g1; ++f) {
             if ((culled >> (8 * (f - g0))) & 1) continue;      // wave-uniform
             const double *P = inv_pose + 16 * (int64_t)f;
-            const float *dimg = kRaw ? nullptr : reinterpret_cast<const float *>(depth) + (int64_t)depth_index[f] * hw;
+            const int64_t slot = kBits ? f : depth_index[f];
+            const float *dimg = kRaw ? nullptr : reinterpret_cast<const float *>(depth) + slot * hw;
             const char *rimg = kRaw ? reinterpret_cast<const char *>(depth) +
-                                      (int64_t)depth_index[f] * raw.frame_stride * (raw.texel_f32 ? 4 : 2) : nullptr;
+                                      slot * raw.frame_stride * (raw.texel_f32 ? 4 : 2) : nullptr;
             int pix[kPPT], pu[kPPT];
             double cz[kPPT];
 #pragma unroll
@@ -699,15 +749,28 @@ __global__ __launch_bounds__(kBlock) void viewed_count_kernel(
                     if (pix[j] >= 0)
                         dval[j] = bilinear_depth(t00[j], t01[j], t10[j], t11[j], ta[j], tb[j]);
             }
+            uint64_t mine = 0;                              // kBits: lane j keeps the ballot of word j
 #pragma unroll
-            for (int j = 0; j < kPPT; ++j)
-                vcount[j] += ((pix[j] >= 0) && (dval[j] != 0.0f) && (fabs(cz[j] - (double)dval[j]) < thresh)) ? 1 : 0;
+            for (int j = 0; j < kPPT; ++j) {
+                const bool vis = (pix[j] >= 0) && (dval[j] != 0.0f) && (fabs(cz[j] - (double)dval[j]) < thresh);
+                vcount[j] += vis ? 1 : 0;
+                if constexpr (kBits) {
+                    const uint64_t bal = __ballot(vis);
+                    if (lane == j) mine = bal;
+                }
+            }
+            // the wave's 32-B sector of the slot's mask row; vis_stride holds the words of whole blocks (a culled frame
+            // keeps the zeros the caller filled in)
+            if constexpr (kBits)
+                if (lane < kPPT) vis_mask[slot * vis_stride + word0 + lane] = mine;
         }
     }
+    if constexpr (!kBits) {
 #pragma unroll
-    for (int j = 0; j < kPPT; ++j) {
-        const int64_t n = (word0 + j) * kWave + lane;
-        if (valid[j] && vcount[j]) atomicAdd(viewed_count + n, vcount[j]);
+        for (int j = 0; j < kPPT; ++j) {
+            const int64_t n = (word0 + j) * kWave + lane;
+            if (valid[j] && vcount[j]) atomicAdd(viewed_count + n, vcount[j]);
+        }
     }
 }
 
@@ -742,6 +805,81 @@ __global__ __launch_bounds__(kBlock) void point_tile_bounds_kernel(const double 
         }
     if (lane < 3) bounds[6 * t + lane] = lane == 0 ? lo[0] : lane == 1 ? lo[1] : lo[2];
     else if (lane < 6) bounds[6 * t + lane] = lane == 3 ? hi[0] : lane == 4 ? hi[1] : hi[2];
+}
+
+// Visibility table, step 2: off[i] = number of set bits in mask[0 .. i), total[0] = all of them.  One block walks the
+// words 4096 at a time (thread t: words 4 t .. 4 t + 3 of the piece, 32 contiguous bytes) with a running carry; n is a
+// multiple of 4.  The table is built once per resident scene, so one block's pace (~0.5 us per piece) is enough.
+constexpr int kScanBlock = 1024;
+
+__global__ __launch_bounds__(kScanBlock) void vis_offsets_kernel(const uint64_t *__restrict__ mask, int64_t n,
+                                                                 uint32_t *__restrict__ off, uint64_t *__restrict__ total)
+{
+    __shared__ uint32_t s_wave[kScanBlock / kWave];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint64_t carry = 0;
+    for (int64_t base = 0; base < n; base += 4 * kScanBlock) {
+        const int64_t i = base + 4 * tid;
+        uint32_t c[4] = {0, 0, 0, 0};
+        if (i < n) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) c[q] = (uint32_t)__popcll(mask[i + q]);
+        }
+        const uint32_t sum = c[0] + c[1] + c[2] + c[3];
+        uint32_t inc = sum;                                    // inclusive scan over the wave, then over the 16 waves
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const uint32_t t = __shfl_up(inc, d);
+            if (lane >= d) inc += t;
+        }
+        if (lane == kWave - 1) s_wave[wave] = inc;
+        __syncthreads();
+        uint32_t before = 0, piece = 0;
+#pragma unroll
+        for (int w = 0; w < kScanBlock / kWave; ++w) {
+            const uint32_t t = s_wave[w];
+            before += w < wave ? t : 0;
+            piece += t;
+        }
+        __syncthreads();                                       // s_wave is rewritten by the next piece
+        if (i < n) {
+            uint32_t at = (uint32_t)carry + before + inc - sum;    // 32-bit offsets: the entry point refuses 2^32 pairs
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                off[i + q] = at;
+                at += c[q];
+            }
+        }
+        carry += piece;
+    }
+    if (tid == 0) total[0] = carry;
+}
+
+// Visibility table, step 3: the pixels of the visible pairs.  One wave per (slot, word) with a non-zero mask word; a
+// lane whose bit is set repeats the sweep's geometry for its point (the same fma chains, divisions and rint: the pixel the
+// mask pass tested) and stores it at the pair's place.  No depth access.
+__global__ __launch_bounds__(kBlock) void vis_pixels_kernel(const double *__restrict__ xyz, int64_t n_pad,
+                                                            const double *__restrict__ inv_pose, Intrinsics K,
+                                                            const uint64_t *__restrict__ mask, const uint32_t *__restrict__ off,
+                                                            int64_t stride, uint32_t *__restrict__ pixels, int64_t pix_cap)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    const int slot = blockIdx.y;
+    if (w >= stride) return;
+    const uint64_t m = mask[slot * stride + w];
+    if (!((m >> lane) & 1)) return;
+    const int64_t n = w * kWave + lane;                        // a set bit is a valid point
+    const double px = xyz[n], py = xyz[n_pad + n], pz = xyz[2 * n_pad + n];
+    const double *P = inv_pose + 16 * (int64_t)slot;
+    const double cx = fma(P[3], 1.0, fma(P[2], pz, fma(P[1], py, fma(P[0], px, 0.0))));
+    const double cy = fma(P[7], 1.0, fma(P[6], pz, fma(P[5], py, fma(P[4], px, 0.0))));
+    const double cz = fma(P[11], 1.0, fma(P[10], pz, fma(P[9], py, fma(P[8], px, 0.0))));
+    const double p0 = fma(K.k[2], cz, fma(K.k[1], cy, fma(K.k[0], cx, 0.0)));
+    const double p1 = fma(K.k[5], cz, fma(K.k[4], cy, fma(K.k[3], cx, 0.0)));
+    const double u = rint(p0 / cz), v = rint(p1 / cz);
+    const int64_t at = (int64_t)off[slot * stride + w] + __popcll(m & ((1ull << lane) - 1));
+    if (at < pix_cap) pixels[at] = (uint32_t)(int)u | ((uint32_t)(int)v << 16);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1150,6 +1288,7 @@ extern "C" int bff_depth_tile_u16(const uint16_t *src, int32_t n_frames, int32_t
     return launched("bff_depth_tile_u16");
 }
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -1213,13 +1352,14 @@ static int project_views_launch(const double *xyz, int64_t n_points, int64_t n_p
                                 const int32_t *frame_flags,
                                 uint64_t *rows, int64_t n_rows, int64_t nw, uint64_t *chunk_mask,
                                 int32_t *masked_count, int32_t *viewed_count, const double *tile_bounds,
-                                void *stream, const MaskRows *mask_rows = nullptr)
+                                void *stream, const MaskRows *mask_rows = nullptr, const VisTable *vis = nullptr)
 {
     BFF_REQUIRE(n_points >= 0 && n_pad >= n_points && n_frames >= 0, "bff_project_views: bad sizes");
     BFF_REQUIRE(height > 0 && width > 0, "bff_project_views: bad image size");
     BFF_LIMIT((int64_t)height * width < (1ll << 31), "bff_project_views: image larger than 2^31 pixels");
     if (n_points == 0 || n_frames == 0) return BFF_OK;
-    BFF_REQUIRE(xyz && inv_pose && cam_intr_host && depth && depth_index && frame_flags, "bff_project_views: null pointer");
+    BFF_REQUIRE((vis || (xyz && inv_pose && cam_intr_host && depth)) && depth_index && frame_flags, "bff_project_views: null pointer");
+    BFF_REQUIRE(!vis || (mask_rows && !raw), "bff_project_views_cached: the cached sweep is a look-up sweep without depth");
     BFF_REQUIRE(nw == ceil_div(n_points, 64), "bff_project_views: nw must be ceil(n_points/64)");
     size_t taps_bytes = 0;
     if (raw) {
@@ -1243,7 +1383,7 @@ static int project_views_launch(const double *xyz, int64_t n_points, int64_t n_p
     }
     const int mw = (int)ceil_div(ceil_div(nw, kCW), 64);
     Intrinsics K;
-    for (int i = 0; i < 9; ++i) K.k[i] = cam_intr_host[i];
+    for (int i = 0; i < 9; ++i) K.k[i] = cam_intr_host ? cam_intr_host[i] : 0.0;
     const int64_t gx = ceil_div(n_points, kPtsPerBlock);
     const int fpb = bff_sweep_frames_per_block(n_points, n_frames);
     dim3 grid((unsigned)gx, (unsigned)ceil_div(n_frames, fpb));
@@ -1254,27 +1394,38 @@ static int project_views_launch(const double *xyz, int64_t n_points, int64_t n_p
     g_sweep_start = g_sweep_stop = nullptr;
     const RawDepth rd = raw ? *raw : RawDepth{};
     const MaskRows mr = mask_rows ? *mask_rows : MaskRows{};
+    const VisTable vt = vis ? *vis : VisTable{};
     static_assert(kRowsFrames >= 8, "a block's frame tile must fit the LDS mask tables");
 #define BFF_SWEEP(WORD, LAB, RAW)                                                                                        \
     hipExtLaunchKernelGGL((project_views_kernel<WORD, LAB, RAW>), grid, dim3(kBlock), (unsigned)taps_bytes, as_stream(stream), \
         ev0, ev1, 0,                                                                                                     \
         xyz, n_points, n_pad, inv_pose, K, n_frames, fpb, depth, rd, depth_index, height, width, depth_thresh,           \
         (const WORD *)maskbits, labels, label_stride, segmap, seg_words, frame_mask, frame_rowbase, frame_nmask,        \
-        frame_flags, rows, nw, chunk_mask, mw, masked_count, viewed_count, tile_bounds, mr)
+        frame_flags, rows, nw, chunk_mask, mw, masked_count, viewed_count, tile_bounds, mr, vt)
 #define BFF_SWEEP_ROWS(WORD, RAW)                                                                                        \
     hipExtLaunchKernelGGL((project_views_kernel<WORD, false, RAW, true>), grid, dim3(kBlock),                            \
         (unsigned)(taps_bytes + rows_bytes), as_stream(stream), ev0, ev1, 0,                                             \
         xyz, n_points, n_pad, inv_pose, K, n_frames, fpb, depth, rd, depth_index, height, width, depth_thresh,           \
         (const WORD *)nullptr, (const uint8_t *)nullptr, label_stride, (const uint32_t *)nullptr, seg_words, frame_mask, \
-        frame_rowbase, frame_nmask, frame_flags, rows, nw, chunk_mask, mw, masked_count, viewed_count, tile_bounds, mr)
+        frame_rowbase, frame_nmask, frame_flags, rows, nw, chunk_mask, mw, masked_count, viewed_count, tile_bounds, mr, vt)
+#define BFF_SWEEP_VIS(WORD)                                                                                              \
+    hipExtLaunchKernelGGL((project_views_kernel<WORD, false, false, true, true>), grid, dim3(kBlock),                    \
+        (unsigned)rows_bytes, as_stream(stream), ev0, ev1, 0,                                                            \
+        xyz, n_points, n_pad, inv_pose, K, n_frames, fpb, depth, rd, depth_index, height, width, depth_thresh,           \
+        (const WORD *)nullptr, (const uint8_t *)nullptr, label_stride, (const uint32_t *)nullptr, seg_words, frame_mask, \
+        frame_rowbase, frame_nmask, frame_flags, rows, nw, chunk_mask, mw, masked_count, viewed_count, tile_bounds, mr, vt)
 #define BFF_SWEEP_LR(WORD)                                                                                               \
     do { if (labels) { if (raw) BFF_SWEEP(WORD, true, true); else BFF_SWEEP(WORD, true, false); }                        \
          else { if (raw) BFF_SWEEP(WORD, false, true); else BFF_SWEEP(WORD, false, false); } } while (0)
-    if (mask_rows) {
+    if (vis) {
+        if (word_bits == 32) BFF_SWEEP_VIS(uint32_t); else BFF_SWEEP_VIS(uint64_t);
+    }
+    else if (mask_rows) {
         if (word_bits == 32) { if (raw) BFF_SWEEP_ROWS(uint32_t, true); else BFF_SWEEP_ROWS(uint32_t, false); }
         else { if (raw) BFF_SWEEP_ROWS(uint64_t, true); else BFF_SWEEP_ROWS(uint64_t, false); }
     }
     else if (!maskbits || word_bits == 32) BFF_SWEEP_LR(uint32_t); else BFF_SWEEP_LR(uint64_t);
+#undef BFF_SWEEP_VIS
 #undef BFF_SWEEP_ROWS
 #undef BFF_SWEEP_LR
 #undef BFF_SWEEP
@@ -1384,6 +1535,100 @@ extern "C" int bff_count_viewed(const double *xyz, int64_t n_points, int64_t n_p
         viewed_count_kernel<false><<<grid, kBlock, 0, st>>>(xyz, n_points, n_pad, inv_pose, K, n_frames, fpb,
             depth, rd, depth_index, height, width, depth_thresh, viewed_count, tile_bounds);
     return launched("bff_count_viewed");
+}
+
+extern "C" int bff_project_views_cached(int64_t n_points, int32_t n_frames, const int32_t *depth_index, int32_t height,
+                                        int32_t width, const uint64_t *vis_mask, const uint32_t *vis_off,
+                                        const uint32_t *vis_pix, const uint32_t *mask_tab, const uint32_t *mask_dir,
+                                        const int32_t *run_start, const int32_t *run_end, const int32_t *view_mask_offs,
+                                        int32_t word_bits, const int32_t *frame_mask, const int32_t *frame_rowbase,
+                                        const int32_t *frame_nmask, const int32_t *frame_flags, uint64_t *rows, int64_t n_rows,
+                                        int64_t nw, uint64_t *chunk_mask, int32_t *masked_count, int32_t *viewed_count,
+                                        void *stream)
+{
+    if (n_points <= 0 || n_frames <= 0) return BFF_OK;
+    BFF_REQUIRE(height > 0 && width > 0, "bff_project_views_cached: bad image size");
+    BFF_REQUIRE(vis_mask && vis_off && vis_pix, "bff_project_views_cached: null table");
+    const MaskRows mr{reinterpret_cast<const uint4 *>(mask_tab), mask_dir, run_start, run_end, view_mask_offs};
+    const VisTable vt{vis_mask, vis_off, vis_pix, bff_visibility_words(n_points)};
+    return project_views_launch(nullptr, n_points, n_points, nullptr, nullptr, n_frames, nullptr, nullptr, depth_index, height,
+                                width, 0.0, nullptr, nullptr, nullptr, word_bits, frame_mask, frame_rowbase, frame_nmask,
+                                frame_flags, rows, n_rows, nw, chunk_mask, masked_count, viewed_count, nullptr, stream, &mr, &vt);
+}
+
+extern "C" int64_t bff_visibility_words(int64_t n_points)
+{
+    return n_points <= 0 ? 0 : ceil_div(n_points, (int64_t)kPtsPerBlock) * kWordsPerBlock;
+}
+
+extern "C" int bff_visibility_table_bytes(int64_t n_points, int32_t n_slots, int64_t n_pixels, int64_t *bytes)
+{
+    BFF_REQUIRE(n_points >= 0 && n_slots >= 0 && n_pixels >= 0 && bytes, "bff_visibility_table_bytes: bad arguments");
+    const int64_t entries = bff_visibility_words(n_points) * n_slots;
+    bytes[0] = (int64_t)sizeof(uint64_t) * entries;
+    bytes[1] = (int64_t)sizeof(uint32_t) * entries;
+    bytes[2] = (int64_t)sizeof(uint32_t) * n_pixels;
+    return BFF_OK;
+}
+
+static std::atomic<int64_t> g_vis_builds{0};
+
+extern "C" int64_t bff_visibility_builds(void) { return g_vis_builds.load(); }
+
+extern "C" int bff_visibility_table(const double *xyz, int64_t n_points, int64_t n_pad, const double *slot_inv_pose,
+                                    const double *cam_intr_host, int32_t n_slots, const void *depth, int32_t depth_h,
+                                    int32_t depth_w, int32_t depth_layout, int32_t height, int32_t width,
+                                    double depth_thresh, const double *tile_bounds, uint64_t *vis_mask, uint32_t *vis_off,
+                                    uint32_t *vis_pix, int64_t pix_cap, uint64_t *n_pixels, int32_t phase, void *stream)
+{
+    BFF_REQUIRE(n_points >= 0 && n_pad >= n_points && n_slots >= 0 && pix_cap >= 0 && phase >= 0 && phase <= 2,
+                "bff_visibility_table: bad sizes");
+    BFF_REQUIRE(height > 0 && width > 0, "bff_visibility_table: bad image size");
+    BFF_LIMIT(height < (1 << 15) && width < (1 << 15), "bff_visibility_table: image too large for packed pixels");
+    BFF_REQUIRE(depth_layout >= -1 && depth_layout <= 2, "bff_visibility_table: depth_layout must be -1, 0, 1 or 2");
+    BFF_LIMIT(n_slots <= 65535, "bff_visibility_table: too many depth slots");
+    if (n_points == 0 || n_slots == 0) return BFF_OK;
+    BFF_REQUIRE(xyz && slot_inv_pose && cam_intr_host && vis_mask && vis_off && n_pixels, "bff_visibility_table: null pointer");
+    hipStream_t st = as_stream(stream);
+    const int64_t stride = bff_visibility_words(n_points), entries = stride * n_slots;
+    Intrinsics K;
+    for (int i = 0; i < 9; ++i) K.k[i] = cam_intr_host[i];
+    if (phase != 2) {
+        BFF_REQUIRE(depth, "bff_visibility_table: null pointer");
+        RawDepth rd{};
+        size_t taps_bytes = 0;
+        if (depth_layout >= 0) {
+            const int rc = raw_depth_params(depth_h, depth_w, height, width, depth_layout, st, &rd);
+            if (rc != BFF_OK) return rc;
+            taps_bytes = sizeof(uint32_t) * ((3 * (size_t)rd.n_taps + 3) / 4 * 4);
+            BFF_LIMIT(taps_bytes <= 48 * 1024, "bff_visibility_table: the resize's tap table exceeds 48 KB of LDS");
+        }
+        hipError_t e = hipMemsetAsync(vis_mask, 0, sizeof(uint64_t) * (size_t)entries, st);     // culled frames store nothing
+        if (e != hipSuccess) return fail((int)e, "bff_visibility_table: memset: %s", hipGetErrorString(e));
+        // 1: the mask pass, bff_count_viewed's kernel with the ballots as output
+        const int fpb = bff_sweep_frames_per_block(n_points, n_slots);
+        dim3 grid((unsigned)ceil_div(n_points, kPtsPerBlock), (unsigned)ceil_div(n_slots, fpb));
+        if (depth_layout >= 0)
+            viewed_count_kernel<true, true><<<grid, kBlock, (unsigned)taps_bytes, st>>>(xyz, n_points, n_pad, slot_inv_pose, K,
+                n_slots, fpb, depth, rd, nullptr, height, width, depth_thresh, nullptr, tile_bounds, vis_mask, stride);
+        else
+            viewed_count_kernel<false, true><<<grid, kBlock, 0, st>>>(xyz, n_points, n_pad, slot_inv_pose, K,
+                n_slots, fpb, depth, rd, nullptr, height, width, depth_thresh, nullptr, tile_bounds, vis_mask, stride);
+        // 2: the offsets
+        vis_offsets_kernel<<<1, kScanBlock, 0, st>>>(vis_mask, entries, vis_off, n_pixels);
+        const int rc = launched("bff_visibility_table");
+        if (rc != BFF_OK) return rc;
+    }
+    if (phase != 1) {
+        // 3: the pixels
+        BFF_REQUIRE(vis_pix || pix_cap == 0, "bff_visibility_table: null pointer");
+        BFF_LIMIT(pix_cap < (1ll << 32), "bff_visibility_table: more than 2^32 visible pairs");
+        dim3 grid((unsigned)ceil_div(stride, kBlock / kWave), (unsigned)n_slots);
+        vis_pixels_kernel<<<grid, kBlock, 0, st>>>(xyz, n_pad, slot_inv_pose, K, vis_mask, vis_off, stride, vis_pix, pix_cap);
+        g_vis_builds.fetch_add(1);
+        return launched("bff_visibility_table");
+    }
+    return BFF_OK;
 }
 
 extern "C" int bff_point_tile_bounds(const double *xyz, int64_t n_points, int64_t n_pad, double *bounds, void *stream)

@@ -121,7 +121,12 @@ extern "C" int bff_scene_project_viewed(const bff_scene *sc, const bff_scene_par
     // (bff_count_viewed over the scene's viewed frames, shared by the classes of the scene)
     int32_t *const sweep_viewed = (ratio && !viewed_in) ? ws->viewed : nullptr;
     const int32_t *const viewed = ratio ? (viewed_in ? viewed_in : ws->viewed) : nullptr;
-    if (lookup)
+    if (lookup && sc->vis_mask && sc->vis_off && sc->vis_pix)      // the scene's visibility table answers geometry and depth
+        BFF_TRY(bff_project_views_cached(n, sc->n_frames, sc->depth_index, sc->height, sc->width, sc->vis_mask, sc->vis_off,
+                                         sc->vis_pix, ws->mask_tab, ws->mask_dir, sc->run_start, sc->run_end,
+                                         sc->view_mask_offs, sc->word_bits, sc->frame_mask, sc->frame_rowbase, sc->frame_nmask,
+                                         sc->frame_flags, ws->rows, n_rows, nw, ws->chunk_mask, ws->masked, sweep_viewed, hv));
+    else if (lookup)
         BFF_TRY(bff_project_views_lookup(sc->xyz, n, sc->n_pad, sc->inv_pose, sc->cam_intr, sc->n_frames,
                                          sc->depth_raw ? sc->depth_raw : (const void *)sc->depth, sc->depth_h, sc->depth_w,
                                          sc->depth_raw ? sc->depth_tiled : -1, sc->depth_index, sc->height, sc->width,

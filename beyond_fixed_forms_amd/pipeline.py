@@ -39,7 +39,8 @@ class SceneStruct(ctypes.Structure):
                 ("s1_run_start", c_void_p), ("s1_run_end", c_void_p), ("s1_row_run_offs", c_void_p),
                 ("height", c_int32), ("width", c_int32), ("n_frames", c_int32), ("n_mviews", c_int32),
                 ("word_bits", c_int32), ("n_rows", c_int32), ("conf_f16", c_int32), ("n_label_ids", c_int32),
-                ("s1_rows", c_int32), ("depth_h", c_int32), ("depth_w", c_int32), ("depth_tiled", c_int32)]
+                ("s1_rows", c_int32), ("depth_h", c_int32), ("depth_w", c_int32), ("depth_tiled", c_int32),
+                ("vis_mask", c_void_p), ("vis_off", c_void_p), ("vis_pix", c_void_p)]
 
 
 class ParamsStruct(ctypes.Structure):
@@ -128,9 +129,10 @@ def _p(t):
     return None if t is None else c_void_p(t.data_ptr())
 
 
-def scene_struct(ds, stage1=None, n_frames=None):
-    """bff_scene of an uploaded scene (+ optionally its resident stage-1 run tables).  The struct only holds
-    pointers: `ds` / `stage1` must stay alive while it is used (callers keep it next to them)."""
+def scene_struct(ds, stage1=None, n_frames=None, vis=None):
+    """bff_scene of an uploaded scene (+ optionally its resident stage-1 run tables and its visibility table, a
+    projection.VisibilityTable).  The struct only holds pointers: `ds` / `stage1` / `vis` must stay alive while it is used
+    (callers keep it next to them)."""
     _check_layout()
     s = SceneStruct()
     s.n_points, s.n_pad, s.nw = ds.n_points, ds.xyz.shape[1], ds.nw
@@ -158,6 +160,8 @@ def scene_struct(ds, stage1=None, n_frames=None):
     if stage1 is not None:
         s.s1_run_start, s.s1_run_end, s.s1_row_run_offs = _p(stage1.run_start), _p(stage1.run_end), _p(stage1.row_run_offs)
         s.s1_rows = stage1.row_run_offs.shape[0] - 1
+    if vis is not None:
+        s.vis_mask, s.vis_off, s.vis_pix = _p(vis.mask), _p(vis.off), _p(vis.pix)
     return s
 
 
@@ -310,16 +314,18 @@ class SceneWorkspace:
         return self.t[name][:n].view(*shape)
 
 
-def issue(ds, cfg, depth_thresh, stage1=None, n_frames=None, viewed_in=None):
+def issue(ds, cfg, depth_thresh, stage1=None, n_frames=None, viewed_in=None, vis=None):
     """Enqueue the whole device side of one scene on the current stream.  Returns a handle for `collect`.
-    viewed_in: the detection ratio's viewed counts, computed beforehand (bff_scene_project_viewed; SceneGeometry)."""
+    viewed_in: the detection ratio's viewed counts, computed beforehand (bff_scene_project_viewed; SceneGeometry).
+    vis: the scene's visibility table for depth_thresh (projection.VisibilityTable), complete on the current stream: the
+    sweep then reads it instead of the cloud and the depth frames."""
     t0 = time.perf_counter() if _TRACE_ISSUE else 0.0
     dev = ds.xyz.device
-    key = (id(stage1), n_frames)
+    key = (id(stage1), n_frames, id(vis))
     cache = ds.__dict__.setdefault("_scene_structs", {})
     ent = cache.get(key)
     if ent is None:
-        ent = cache[key] = (scene_struct(ds, stage1, n_frames), stage1)      # keeps stage1's tensors alive too
+        ent = cache[key] = (scene_struct(ds, stage1, n_frames, vis), stage1, vis)      # keeps their tensors alive too
     sc = ent[0]
     s1_rows = int(sc.s1_rows)
     cap = int(ds.__dict__.get("_group_cap", GROUP_CAP))           # GROUP_CAP_MAX once the scene was seen to keep more groups
@@ -353,7 +359,7 @@ def issue(ds, cfg, depth_thresh, stage1=None, n_frames=None, viewed_in=None):
         now = time.perf_counter()
         print(f"slow issue: {1e3 * (now - t0):.2f} ms, of which the native call {1e3 * (now - t1):.2f} ms", file=sys.stderr)
     return dict(ws=ws, both=both, s1_rows=s1_rows, params=pr, stream=ws.stream, cap=cap,
-                args=(ds, cfg, depth_thresh, stage1, n_frames, viewed_in))
+                args=(ds, cfg, depth_thresh, stage1, n_frames, viewed_in, vis))
 
 
 def collect(h):

@@ -188,6 +188,71 @@ def fast_path_ok(ds: DeviceScene) -> bool:
             and ds.xyz.is_cuda and os.environ.get("BFF_NO_FAST") != "1")
 
 
+@dataclasses.dataclass
+class VisibilityTable:
+    """The visibility table of a resident scene for one depth threshold (_lib.visibility_table; include/bff_hip.h)."""
+    mask: torch.Tensor            # int64 [slots][visibility_words]
+    off: torch.Tensor             # int32 [slots][visibility_words]
+    pix: torch.Tensor             # int32 [visible pairs]
+    ready: torch.cuda.Event       # recorded behind the build
+    streams: set                  # raw handles of the streams that are already ordered behind the build
+
+
+def vis_table_max_bytes():
+    """BFF_VIS_TABLE_MAX_MB (default 512): a scene whose table would be larger keeps the plain sweep."""
+    return int(float(os.environ.get("BFF_VIS_TABLE_MAX_MB", "512")) * (1 << 20))
+
+
+def scene_visibility(ds: DeviceScene, depth_thresh) -> Optional[VisibilityTable]:
+    """The visibility table the fast path sweeps `ds` with on the current stream, or None for the plain sweep.
+
+    The table belongs to what no mask touches -- the scene's geometry when `ds` shares one (every class of the geometry
+    then reads the same table), else `ds` itself -- and to depth_thresh.  A scene projected once pays nothing: the first
+    call only notes the visit, the second builds the table on its stream (one wait for the number of visible pairs) and
+    every later call, on any stream, reads it; other streams are ordered behind the build by its event, once each.  Like
+    the cached scene structs this relies on the tensors of a resident scene not being edited in place.  BFF_VIS_TABLE=0
+    switches it off; scenes whose masks are decoded (no row directory) or whose table exceeds vis_table_max_bytes() keep
+    the plain sweep."""
+    if os.environ.get("BFF_VIS_TABLE", "1") == "0" or not _lib.mask_lookup_rows(ds.height, ds.width, ds.n_rows):
+        return None
+    owner = ds.geometry if ds.geometry is not None else ds
+    tables = owner.__dict__.setdefault("_vis_tables", {})
+    key = float(depth_thresh)
+    tab = tables.get(key)
+    if tab is None:
+        tables[key] = "visited"
+        return None
+    if tab is False:
+        return None
+    raw = _lib.raw_stream()
+    if tab == "visited":
+        dev = ds.xyz.device
+        if ds.geometry is not None:
+            poses = torch.as_tensor(np.ascontiguousarray(owner.inv_pose_host, dtype=np.float64).reshape(-1, 16)).to(dev)
+        else:
+            # one pose per depth slot: that of the first frame that reads the slot (a frame id has one pose)
+            di = ds.depth_index.cpu().numpy()
+            first = np.zeros(int(ds.sweep_depth.shape[0]), dtype=np.int64)
+            slots, idx = np.unique(di, return_index=True)
+            first[slots] = idx
+            poses = ds.inv_pose[torch.as_tensor(first).to(dev)].contiguous()
+        got = _lib.visibility_table(ds.xyz, ds.n_points, poses, ds.cam_intr, ds.sweep_depth, ds.height, ds.width, key,
+                                    ds.tile_bounds, depth_size=ds.depth_size, max_bytes=vis_table_max_bytes())
+        if got is None:
+            tables[key] = False
+            return None
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(dev))
+        tab = tables[key] = VisibilityTable(*got, ready=ready, streams={raw})
+    elif raw not in tab.streams:
+        st = torch.cuda.current_stream(ds.xyz.device)
+        st.wait_event(tab.ready)
+        for t in (tab.mask, tab.off, tab.pix):
+            t.record_stream(st)
+        tab.streams.add(raw)
+    return tab
+
+
 def projection_front(ds: DeviceScene, cfg, debug_out: bool = False, timers=None, stage1=None, fast=None) -> _Front:
     """Issue the device work of P:402-634 for one uploaded scene.  Nothing here waits for the GPU, so a caller can
     issue the next scene on another stream while the host finishes this one (`projection_back`).
@@ -208,9 +273,11 @@ def projection_front(ds: DeviceScene, cfg, debug_out: bool = False, timers=None,
                          "(prepare the geometry with with_viewed=True)")
     if fast and fast_path_ok(ds) and (stage1 is None or stage1.n_points == ds.n_points):
         fr = _Front(ds, cfg, {}, False, do_ratio=do_ratio, stage1=stage1)
+        vis = scene_visibility(ds, DEPTH_THRESH)
+        fr.dbg["sweep"] = "plain" if vis is None else "cached"
         with sweep_span(timers, "project_views"), merge_span(timers, "merge_components"):
             fr.fast = pipeline.issue(ds, cfg, DEPTH_THRESH, stage1,
-                                     ds.n_frames if (do_ratio and viewed_in is None) else ds.n_mask_frames, viewed_in)
+                                     ds.n_frames if (do_ratio and viewed_in is None) else ds.n_mask_frames, viewed_in, vis)
         return fr
     with _lib.launch_stream():
         fr = _projection_front(ds, cfg, debug_out, timers, viewed_in=viewed_in)

@@ -788,6 +788,42 @@ int bff_project_views_lookup(const double *xyz, int64_t n_points, int64_t n_pad,
                              int32_t *masked_count, int32_t *viewed_count, const double *tile_bounds,
                              void *stream);
 
+/* The visibility table of a resident scene: what the sweep's geometry and depth test answer per (depth slot, point),
+ * kept from call to call (it depends on the cloud, the poses, the depth frames and depth_thresh -- not on the masks).
+ * For slot s (what depth_index[f] holds), sorted point word w and lane l, with stride = bff_visibility_words(n_points)
+ * (the words of whole sweep blocks, >= ceil(n_points / 64)):
+ *   vis_mask uint64 [n_slots][stride]  bit l set iff point 64 w + l passes exactly the sweep's test in that frame (valid,
+ *            u and v in bounds on the doubles, depth != 0, |z - depth| < depth_thresh)
+ *   vis_off  uint32 [n_slots][stride]  exclusive prefix of the popcounts in (slot, word) order
+ *   vis_pix  uint32 [n_pixels]         each visible pair's pixel u | v << 16 at vis_off + popcount(mask & lanes below l)
+ * height, width < 2^15, fewer than 2^32 visible pairs.
+ * bff_visibility_table builds it on `stream`: 1 the mask pass (bff_count_viewed's kernel and arithmetic, storing the ballots;
+ * frame s reads depth slot s with pose slot_inv_pose[s]), 2 the offsets and *n_pixels (device, uint64), 3 the pixel pass
+ * (geometry only, for words with a set bit; pairs at or beyond pix_cap are dropped).  phase 0: all three with a caller's
+ * bound pix_cap; phase 1: steps 1 and 2 (vis_pix unused); phase 2: step 3 alone, after the caller has read *n_pixels and
+ * allocated vis_pix.  Nothing in it waits for the host.  `depth`, `depth_h`, `depth_w`, `depth_layout`, `tile_bounds` as
+ * bff_project_views_lookup. */
+int64_t bff_visibility_words(int64_t n_points);
+/* bytes[3] = sizes of vis_mask, vis_off and of vis_pix for n_pixels visible pairs */
+int bff_visibility_table_bytes(int64_t n_points, int32_t n_slots, int64_t n_pixels, int64_t *bytes);
+int bff_visibility_table(const double *xyz, int64_t n_points, int64_t n_pad, const double *slot_inv_pose,
+                         const double *cam_intr_host, int32_t n_slots, const void *depth, int32_t depth_h,
+                         int32_t depth_w, int32_t depth_layout, int32_t height, int32_t width, double depth_thresh,
+                         const double *tile_bounds, uint64_t *vis_mask, uint32_t *vis_off, uint32_t *vis_pix,
+                         int64_t pix_cap, uint64_t *n_pixels, int32_t phase, void *stream);
+/* pixel passes issued by this process so far (one per table built) */
+int64_t bff_visibility_builds(void);
+/* bff_project_views_lookup answered from the table: same grid, frame tiles, outputs (bit for bit) and profiling events; the
+ * cloud, the poses and the depth frames are not read.  The table must have been built for the scene's cloud, the frames'
+ * poses and depth slots, and the depth_thresh the caller would have swept with. */
+int bff_project_views_cached(int64_t n_points, int32_t n_frames, const int32_t *depth_index, int32_t height,
+                             int32_t width, const uint64_t *vis_mask, const uint32_t *vis_off, const uint32_t *vis_pix,
+                             const uint32_t *mask_tab, const uint32_t *mask_dir, const int32_t *run_start,
+                             const int32_t *run_end, const int32_t *view_mask_offs, int32_t word_bits,
+                             const int32_t *frame_mask, const int32_t *frame_rowbase, const int32_t *frame_nmask,
+                             const int32_t *frame_flags, uint64_t *rows, int64_t n_rows, int64_t nw, uint64_t *chunk_mask,
+                             int32_t *masked_count, int32_t *viewed_count, void *stream);
+
 /* Device-resident inputs of one scene (what scene.prepare_scene uploads; all pointers are device pointers). */
 typedef struct bff_scene {
     int64_t n_points, n_pad, nw;
@@ -806,6 +842,8 @@ typedef struct bff_scene {
     const int32_t *s1_run_start, *s1_run_end, *s1_row_run_offs;     /* stage-1 run tables or NULL */
     int32_t height, width, n_frames, n_mviews, word_bits, n_rows, conf_f16, n_label_ids, s1_rows, depth_h, depth_w,
             depth_tiled;            /* depth_layout of bff_project_views_u16: 0 uint16 rows, 1 uint16 tiles, 2 float32 tiles */
+    const uint64_t *vis_mask;       /* the scene's visibility table (bff_visibility_table, built for params.depth_thresh) or */
+    const uint32_t *vis_off, *vis_pix;     /* NULL: with all three set and masks looked up, the sweep is bff_project_views_cached */
 } bff_scene;
 
 typedef struct bff_scene_params {
