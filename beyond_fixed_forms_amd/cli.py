@@ -437,6 +437,54 @@ def split_main(argv=None):
     return 0
 
 
+def _cluster_parser():
+    p = _parser("Beyond-Fixed-Forms 3-D instances clustered by density, DBSCAN with a deterministic border rule (MI355X)")
+    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
+                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
+    return p
+
+
+def cluster_main(argv=None):
+    """python tools/cluster_instances_3d.py --config configs/config.yaml --cls "<class>" [--stage final|mask_3d]
+    For every scene of the class's output directory: the search index of the cloud at cluster_eps metres built once, every
+    instance cut into its density clusters (density.cluster_instances: noise dropped) and saved to
+    cluster_output_dir/<cls>/<scene>.pth in the stage's own file format, with the clusters' parent instances under the
+    added key "parent".  Only the cloud is read."""
+    from . import density
+    args = _cluster_parser().parse_args(argv)
+    cfg = load_config(args.config)
+    cls = args.cls
+    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
+    if not os.path.isdir(data_path):
+        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
+        return 1
+    out_dir = cfg.get("cluster_output_dir")
+    if not out_dir:
+        raise ValueError("cluster_output_dir is not set in the config")
+    eps = density.cluster_eps(cfg)
+    # a bad value stops the run before the first scene
+    density.cluster_min_samples(cfg), density.cluster_min_points(cfg), density.cluster_mode(cfg)
+    _lib.load()
+    _host_threads()
+    device = "cuda"
+    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
+        scene_id = name[:-4]
+        print("Working on", scene_id, "class", cls)
+        index = density.density_index(np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy")), eps, device)
+        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+        inst = _saved_instances(result, index.n_points, device)
+        if inst.rows is None:                                            # the reference's empty forms pass through
+            save_result(result, out_dir, cls, scene_id)
+            continue
+        parts = density.cluster_instances(index, inst, cfg)
+        ins = _lib.rows_to_rle(parts.rows, index.n_points) if os.environ.get("BFF_SAVE_RLE") == "1" else \
+            _lib.unpack_rows(parts.rows, index.n_points).cpu()
+        conf = parts.conf.cpu() if torch.is_tensor(parts.conf) else parts.conf
+        save_result({"ins": ins, "conf": conf, "final_class": parts.final_class, "parent": parts.parent}, out_dir, cls,
+                    scene_id)
+    return 0
+
+
 def _snap_parser():
     p = _parser("Beyond-Fixed-Forms 3-D instances snapped to superpoints (MI355X)")
     p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),

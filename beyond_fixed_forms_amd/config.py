@@ -59,6 +59,13 @@ DEFAULTS = dict(
     # than this from every point of the small one joins no instance, absent = 2 x subsample_voxel; lift_target_npy_dir:
     # where the full clouds lie; lift_output_dir: where the second tool saves <cls>/<scene>.pth
     subsample_voxel=None, subsample_npy_dir=None, lift_max_dist=None, lift_target_npy_dir=None, lift_output_dir=None,
+    # not keys of the reference either: 3-D instances clustered by density, DBSCAN with a deterministic border rule
+    # (density.py, tools/cluster_instances_3d.py).  cluster_eps: metres > 0, the neighbourhood radius -- a few point
+    # spacings, e.g. 0.1; cluster_min_samples: integer >= 1, a point with that many of its instance's points within
+    # cluster_eps (itself included) is a core point; both untuned, and required by the tool; cluster_min_points: a cluster
+    # with fewer points is dropped; cluster_mode: "split" (every cluster becomes an instance) or "largest" (only the
+    # largest cluster of each); cluster_output_dir: where the tool saves <cls>/<scene>.pth
+    cluster_eps=None, cluster_min_samples=None, cluster_min_points=1, cluster_mode="split", cluster_output_dir=None,
 )
 
 

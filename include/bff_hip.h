@@ -1114,6 +1114,77 @@ int bff_rows_to_columns(const uint64_t *rows_in, int32_t n_rows, int64_t nw_in, 
 int bff_lift_bits(const uint64_t *cols, int64_t n_source, int32_t n_rows, const int32_t *nn, int64_t n_target,
                   uint64_t *rows_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 3-D instances clustered by density: DBSCAN(eps, min_samples) with a deterministic border rule (DESIGN.md section 7j;
+ * no counterpart in the reference).  A pure function of the inputs, independent of point order, thread schedule and run;
+ * tests/density_ref.py restates it in NumPy by brute force and the results are equal bit for bit.
+ *
+ * Inputs: points float64 [N][stride >= 3] in the caller's point order; eps > 0, finite, in metres; min_samples >= 1; rows
+ * u64 [K][nw], nw >= ceil(N / 64), whose bits at positions >= N are ignored whatever they hold and are zero in every
+ * output; min_points >= 1; a mode.
+ *
+ * Finite points.  A point is finite when all three coordinates are.  A non-finite point has no cell, is nobody's
+ * neighbour and appears in no output row.
+ * Distance.  d2(p, q) = (dx * dx + dy * dy) + dz * dz with dx = x[p] - x[q], every operation rounded to float64, no fma
+ * (bff_nn_search's expression; the unit is compiled with -ffp-contract=off).
+ * Neighbours.  p and q are neighbours when d2 <= float64(eps) * float64(eps).  A point is its own neighbour.
+ *
+ * Rows are independent: a point shared by two rows links nothing between them.  Per row k, over its finite set points:
+ *   Core.     count[p] = the row's points that are neighbours of p, p included; p is core when count[p] >= min_samples
+ *             (sklearn's convention).
+ *   Clusters. Two core points are linked when they are neighbours; a cluster is a class of the transitive closure over
+ *             the core points, its anchor its smallest core point index.
+ *   Border.   A non-core point with at least one core neighbour joins the cluster of its nearest core neighbour: the
+ *             smallest d2, equal d2 going to the smallest point index.  (sklearn gives such a point to whichever cluster
+ *             reaches it first in index order: the one deliberate difference, and why the result does not depend on a
+ *             traversal.)
+ *   Noise.    Everything else; it is in no output row.
+ *
+ * Output, in the split's shape: mode "split": every cluster with at least min_points points (core + border) becomes a
+ * row, ordered by parent row ascending, point count descending, anchor ascending; mode "largest": per parent row only the
+ * first of those.  The choice and the order are the host's (density.cluster_rows); the entry points below are the steps.
+ *
+ * The search index is the lift's (bff_nn_search above): the grid (bff_voxel_*) of the cloud with the points of every cell
+ * in ascending point index and the cloud gathered into that order.  Its cell is float64(eps) * (1 + 2^-20), not eps: two
+ * points within eps of each other then differ by less than 1 - 9e-7 cells on every axis before rounding, the quotient
+ * floor((x - lo) / cell) carries an error below 2^-31 cells (q < 2^21), so their cells differ by at most 1 on every axis
+ * and the 27 cells around a point hold every neighbour -- with cell = eps a pair at d2 == eps^2 can round two cells
+ * apart.  The distance test is the statement's, so the larger cell changes no result.
+ *
+ * How the steps are cut.  All passes run one wave per 64-bit word of a row, lane = point, in the caller's point order.
+ *   bff_dbscan_elements  set = rows & finite with the bits >= N cleared; the elements are its set bits, numbered in (row,
+ *                        point) order: e = elem_offs[k] + prefix[k][p >> 6] + popcount(set[k][p >> 6] below bit (p & 63))
+ *   bff_dbscan_core      the density pass: core u64 [K][ceil(N / 64)]
+ *   bff_dbscan_link      unions over the core elements (compare-and-swap, the larger root under the smaller), a flatten
+ *                        that only reads, then every non-core element's slot written by its own thread: parent[e] = the
+ *                        smallest core element of e's cluster, -1 for noise
+ *   bff_split_count, bff_split_emit   unchanged, called with vox[p] = p (-1 for a non-finite point), n_voxels = N, rows =
+ *                        occ = set: they accept any point-to-cell map, a parent of -1 is followed nowhere, and a root
+ *                        is an element with parent[e] == e.  Within a row, element order is point order, so the root of a
+ *                        cluster is its anchor.
+ * Limits: N < 2^31; the grid's 2^21 cells per axis (bff_voxel_keys); K * ceil(N / 64) * 64 < 2^31 bits, which bounds the
+ * elements T; else BFF_E_LIMIT from a host-side check before any launch.  Zero sizes return 0 without a launch.  No entry
+ * point allocates or synchronises. */
+
+/* finite: u64 [ceil(N / 64)], bit p = point p has a cell.  set: u64 [K][ceil(N / 64)]; prefix: i32 [K][ceil(N / 64)], the
+ * row's set bits below each word; row_total: i32 [K].  The caller turns row_total into elem_offs i32 [K + 1] (exclusive
+ * prefix sum; elem_offs[K] = T). */
+int bff_dbscan_elements(const uint64_t *rows, int32_t n_rows, int64_t nw, int64_t n_points, const uint64_t *finite,
+                        uint64_t *set, int32_t *prefix, int32_t *row_total, void *stream);
+/* points: f64 [n_points][stride >= 3], the queries.  cloud, keys, offs, order, n_voxels, n_source, lo_host, cell: the
+ * index as bff_nn_search takes it (src = cloud), n_source <= n_points the finite points, cell >= eps.  core: u64
+ * [K][ceil(N / 64)], cleared here.  The count of a point stops at min_samples; the row's bit of a candidate is tested
+ * before its distance.  An entry of order outside [0, N) is nobody's neighbour.  With n_voxels = 0 core stays zero. */
+int bff_dbscan_core(const uint64_t *set, int32_t n_rows, int64_t n_points, const double *points, int64_t stride,
+                    const double *cloud, const int64_t *keys, const int32_t *offs, const int32_t *order, int64_t n_voxels,
+                    int64_t n_source, const double *lo_host, double cell, double eps, int32_t min_samples, uint64_t *core,
+                    void *stream);
+/* parent: i32 [n_elems], n_elems = T, written whole. */
+int bff_dbscan_link(const uint64_t *set, const uint64_t *core, const int32_t *prefix, const int32_t *elem_offs, int32_t n_rows,
+                    int64_t n_points, const double *points, int64_t stride, const double *cloud, const int64_t *keys,
+                    const int32_t *offs, const int32_t *order, int64_t n_voxels, int64_t n_source, const double *lo_host,
+                    double cell, double eps, int32_t n_elems, int32_t *parent, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
