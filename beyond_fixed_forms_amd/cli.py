@@ -15,9 +15,10 @@ mask_2d file), the class checkpoint by rank 0.
 The third stage, `evaluation_main` (the reference's evaluation/eval/eval_scannet200.py), scores a class's final files
 against the ground truth in one process: AP, AP50, AP25 and the recalls into the class's line of the results file.
 Beside the path: `reproject_main` renders a stage's instances back into the colour frames as 2-D masks, `split_main` cuts
-them into their spatially connected parts, `snap_main` snaps them to the scan's superpoints, `subsample_main` writes a
-voxel subsample of every cloud and `lift_main` carries the instances of a run on it back to the full cloud; each writes
-to a directory of its own.
+them into their spatially connected parts, `cluster_main` into their density clusters, `snap_main` snaps them to the
+scan's superpoints, `subsample_main` writes a voxel subsample of every cloud and `lift_main` carries the instances of a run
+on it back to the full cloud; each writes to a directory of its own.  The four that turn a stage's files into files of
+the same format (split, cluster, snap, lift) are one driver, `_stage_main`, with a per-scene function each.
 """
 from __future__ import annotations
 
@@ -42,6 +43,13 @@ def _parser(desc):
     p = argparse.ArgumentParser(description=desc)                 # P:314-318 / R:128-132
     p.add_argument("--config", type=str, required=True, help="Config")
     p.add_argument("--cls", type=str, required=True, help="Class")
+    return p
+
+
+def _stage_parser(desc):
+    p = _parser(desc)
+    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
+                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
     return p
 
 
@@ -319,9 +327,7 @@ def refinement_main(argv=None):
 
 
 def _reproject_parser():
-    p = _parser("Beyond-Fixed-Forms 3D->2D reprojection: a class's instances as 2-D masks of the colour frames (MI355X)")
-    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
-                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
+    p = _stage_parser("Beyond-Fixed-Forms 3D->2D reprojection: a class's instances as 2-D masks of the colour frames (MI355X)")
     p.add_argument("--every", type=int, default=None,
                    help="Render into every n-th colour frame (default: downsample_ratio, the frames the 2-D stage saw)")
     return p
@@ -391,11 +397,53 @@ def reproject_main(argv=None):
     return 0
 
 
+def _stage_main(parser, argv, dir_keys, check, scene):
+    """What split_main, cluster_main, snap_main and lift_main share.  dir_keys: the config's directories the stage needs,
+    its output directory first; check(cfg): the stage's config values, so that a bad one stops the run before the first
+    scene; scene(cfg, scene_id, result, device): the saved file of one scene -> (its instances with the rows replaced,
+    the length of their cloud), or None for a file that passes through as it is (the reference's empty forms).  The new
+    instances are saved in the stage's own file format, with the attribute `parent`, where the stage sets one, under the
+    added key "parent"."""
+    args = parser.parse_args(argv)
+    cfg = load_config(args.config)
+    cls = args.cls
+    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
+    if not os.path.isdir(data_path):
+        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
+        return 1
+    for key in dir_keys:
+        if not cfg.get(key):
+            raise ValueError(f"{key} is not set in the config")
+    out_dir = cfg.get(dir_keys[0])
+    check(cfg)
+    _lib.load()
+    _host_threads()
+    device = "cuda"
+    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
+        scene_id = name[:-4]
+        print("Working on", scene_id, "class", cls)
+        # the stage's own output file, written by this project's scripts or the reference's (a pickled dict of tensors)
+        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+        done = scene(cfg, scene_id, result, device)
+        if done is None:
+            save_result(result, out_dir, cls, scene_id)
+            continue
+        inst, n_points = done
+        ins = _lib.rows_to_rle(inst.rows, n_points) if os.environ.get("BFF_SAVE_RLE") == "1" else \
+            _lib.unpack_rows(inst.rows, n_points).cpu()
+        out = {"ins": ins, "conf": inst.conf.cpu() if torch.is_tensor(inst.conf) else inst.conf, "final_class": inst.final_class}
+        if hasattr(inst, "parent"):
+            out["parent"] = inst.parent
+        save_result(out, out_dir, cls, scene_id)
+    return 0
+
+
+def _scene_cloud(cfg, scene_id, **kw):
+    return np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"), **kw)
+
+
 def _split_parser():
-    p = _parser("Beyond-Fixed-Forms 3-D instances split into spatially connected parts (MI355X)")
-    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
-                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
-    return p
+    return _stage_parser("Beyond-Fixed-Forms 3-D instances split into spatially connected parts (MI355X)")
 
 
 def split_main(argv=None):
@@ -404,44 +452,18 @@ def split_main(argv=None):
     instance cut into its connected parts (spatial.split_instances) and saved to split_output_dir/<cls>/<scene>.pth in the
     stage's own file format, with the parts' parent instances under the added key "parent".  Only the cloud is read."""
     from . import spatial
-    args = _split_parser().parse_args(argv)
-    cfg = load_config(args.config)
-    cls = args.cls
-    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
-    if not os.path.isdir(data_path):
-        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
-        return 1
-    out_dir = cfg.get("split_output_dir")
-    if not out_dir:
-        raise ValueError("split_output_dir is not set in the config")
-    cell = spatial.split_voxel(cfg)
-    spatial.split_min_points(cfg), spatial.split_mode(cfg)              # a bad value stops the run before the first scene
-    _lib.load()
-    _host_threads()
-    device = "cuda"
-    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
-        scene_id = name[:-4]
-        print("Working on", scene_id, "class", cls)
-        grid = spatial.voxel_grid(np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy")), cell, device)
-        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+
+    def scene(cfg, scene_id, result, device):
+        grid = spatial.voxel_grid(_scene_cloud(cfg, scene_id), spatial.split_voxel(cfg), device)
         inst = _saved_instances(result, grid.n_points, device)
-        if inst.rows is None:                                            # the reference's empty forms pass through
-            save_result(result, out_dir, cls, scene_id)
-            continue
-        parts = spatial.split_instances(grid, inst, cfg)
-        ins = _lib.rows_to_rle(parts.rows, grid.n_points) if os.environ.get("BFF_SAVE_RLE") == "1" else \
-            _lib.unpack_rows(parts.rows, grid.n_points).cpu()
-        conf = parts.conf.cpu() if torch.is_tensor(parts.conf) else parts.conf
-        save_result({"ins": ins, "conf": conf, "final_class": parts.final_class, "parent": parts.parent}, out_dir, cls,
-                    scene_id)
-    return 0
+        return None if inst.rows is None else (spatial.split_instances(grid, inst, cfg), grid.n_points)
+
+    check = lambda cfg: (spatial.split_voxel(cfg), spatial.split_min_points(cfg), spatial.split_mode(cfg))
+    return _stage_main(_split_parser(), argv, ("split_output_dir",), check, scene)
 
 
 def _cluster_parser():
-    p = _parser("Beyond-Fixed-Forms 3-D instances clustered by density, DBSCAN with a deterministic border rule (MI355X)")
-    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
-                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
-    return p
+    return _stage_parser("Beyond-Fixed-Forms 3-D instances clustered by density, DBSCAN with a deterministic border rule (MI355X)")
 
 
 def cluster_main(argv=None):
@@ -451,45 +473,19 @@ def cluster_main(argv=None):
     cluster_output_dir/<cls>/<scene>.pth in the stage's own file format, with the clusters' parent instances under the
     added key "parent".  Only the cloud is read."""
     from . import density
-    args = _cluster_parser().parse_args(argv)
-    cfg = load_config(args.config)
-    cls = args.cls
-    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
-    if not os.path.isdir(data_path):
-        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
-        return 1
-    out_dir = cfg.get("cluster_output_dir")
-    if not out_dir:
-        raise ValueError("cluster_output_dir is not set in the config")
-    eps = density.cluster_eps(cfg)
-    # a bad value stops the run before the first scene
-    density.cluster_min_samples(cfg), density.cluster_min_points(cfg), density.cluster_mode(cfg)
-    _lib.load()
-    _host_threads()
-    device = "cuda"
-    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
-        scene_id = name[:-4]
-        print("Working on", scene_id, "class", cls)
-        index = density.density_index(np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy")), eps, device)
-        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+
+    def scene(cfg, scene_id, result, device):
+        index = density.density_index(_scene_cloud(cfg, scene_id), density.cluster_eps(cfg), device)
         inst = _saved_instances(result, index.n_points, device)
-        if inst.rows is None:                                            # the reference's empty forms pass through
-            save_result(result, out_dir, cls, scene_id)
-            continue
-        parts = density.cluster_instances(index, inst, cfg)
-        ins = _lib.rows_to_rle(parts.rows, index.n_points) if os.environ.get("BFF_SAVE_RLE") == "1" else \
-            _lib.unpack_rows(parts.rows, index.n_points).cpu()
-        conf = parts.conf.cpu() if torch.is_tensor(parts.conf) else parts.conf
-        save_result({"ins": ins, "conf": conf, "final_class": parts.final_class, "parent": parts.parent}, out_dir, cls,
-                    scene_id)
-    return 0
+        return None if inst.rows is None else (density.cluster_instances(index, inst, cfg), index.n_points)
+
+    check = lambda cfg: (density.cluster_eps(cfg), density.cluster_min_samples(cfg), density.cluster_min_points(cfg),
+                         density.cluster_mode(cfg))
+    return _stage_main(_cluster_parser(), argv, ("cluster_output_dir",), check, scene)
 
 
 def _snap_parser():
-    p = _parser("Beyond-Fixed-Forms 3-D instances snapped to superpoints (MI355X)")
-    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
-                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
-    return p
+    return _stage_parser("Beyond-Fixed-Forms 3-D instances snapped to superpoints (MI355X)")
 
 
 def snap_main(argv=None):
@@ -499,45 +495,20 @@ def snap_main(argv=None):
     snap_output_dir/<cls>/<scene>.pth in the stage's own file format, with the surviving rows' input instances under the
     added key "parent".  Only the cloud's length and the superpoint file are read."""
     from . import superpoints
-    args = _snap_parser().parse_args(argv)
-    cfg = load_config(args.config)
-    cls = args.cls
-    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
-    if not os.path.isdir(data_path):
-        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
-        return 1
-    out_dir, spp_dir = cfg.get("snap_output_dir"), cfg.get("superpoint_dir")
-    if not out_dir:
-        raise ValueError("snap_output_dir is not set in the config")
-    if not spp_dir:
-        raise ValueError("superpoint_dir is not set in the config")
-    # a bad value stops the run before the first scene
-    superpoints.snap_ratio(cfg), superpoints.snap_mode(cfg), superpoints.snap_min_points(cfg)
-    _lib.load()
-    _host_threads()
-    device = "cuda"
-    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
-        scene_id = name[:-4]
-        print("Working on", scene_id, "class", cls)
-        n_points = int(np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"), mmap_mode="r").shape[0])
+
+    def scene(cfg, scene_id, result, device):
+        n_points = int(_scene_cloud(cfg, scene_id, mmap_mode="r").shape[0])
         # the dataset's own file: an ndarray or a tensor of ids (scannet_loader.py:92 accepts both)
-        spp = torch.load(os.path.join(spp_dir, f"{scene_id}.pth"), map_location="cpu", weights_only=False)
+        spp = torch.load(os.path.join(cfg.get("superpoint_dir"), f"{scene_id}.pth"), map_location="cpu", weights_only=False)
         n_ids = int(spp.numel()) if torch.is_tensor(spp) else int(np.asarray(spp).size)
         if n_ids != n_points:
             raise ValueError(f"{scene_id}: a superpoint file of {n_ids} ids for a cloud of {n_points} points")
         index = superpoints.superpoint_index(spp, device)
-        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
         inst = _saved_instances(result, n_points, device)
-        if inst.rows is None:                                            # the reference's empty forms pass through
-            save_result(result, out_dir, cls, scene_id)
-            continue
-        snapped = superpoints.snap_instances(index, inst, cfg)
-        ins = _lib.rows_to_rle(snapped.rows, n_points) if os.environ.get("BFF_SAVE_RLE") == "1" else \
-            _lib.unpack_rows(snapped.rows, n_points).cpu()
-        conf = snapped.conf.cpu() if torch.is_tensor(snapped.conf) else snapped.conf
-        save_result({"ins": ins, "conf": conf, "final_class": snapped.final_class, "parent": snapped.parent}, out_dir, cls,
-                    scene_id)
-    return 0
+        return None if inst.rows is None else (superpoints.snap_instances(index, inst, cfg), n_points)
+
+    check = lambda cfg: (superpoints.snap_ratio(cfg), superpoints.snap_mode(cfg), superpoints.snap_min_points(cfg))
+    return _stage_main(_snap_parser(), argv, ("snap_output_dir", "superpoint_dir"), check, scene)
 
 
 def _subsample_parser():
@@ -581,10 +552,7 @@ def subsample_main(argv=None):
 
 
 def _lift_parser():
-    p = _parser("Beyond-Fixed-Forms 3-D instances lifted from a subsampled cloud to the full cloud (MI355X)")
-    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
-                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
-    return p
+    return _stage_parser("Beyond-Fixed-Forms 3-D instances lifted from a subsampled cloud to the full cloud (MI355X)")
 
 
 def _saved_mask_length(result):
@@ -603,46 +571,23 @@ def lift_main(argv=None):
     within lift_max_dist, every instance lifted (lift.lift_instances) and saved to lift_output_dir/<cls>/<scene>.pth in
     the stage's own file format, the masks of the full cloud's length.  Only the two clouds are read."""
     from . import lift
-    args = _lift_parser().parse_args(argv)
-    cfg = load_config(args.config)
-    cls = args.cls
-    data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
-    if not os.path.isdir(data_path):
-        print(f"no {args.stage} output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
-        return 1
-    out_dir, target_dir = cfg.get("lift_output_dir"), cfg.get("lift_target_npy_dir")
-    if not out_dir:
-        raise ValueError("lift_output_dir is not set in the config")
-    if not target_dir:
-        raise ValueError("lift_target_npy_dir is not set in the config")
-    radius = lift.lift_max_dist(cfg)                                     # a bad value stops the run before the first scene
-    _lib.load()
-    _host_threads()
-    device = "cuda"
-    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
-        scene_id = name[:-4]
-        print("Working on", scene_id, "class", cls)
-        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+
+    def scene(cfg, scene_id, result, device):
         length = _saved_mask_length(result)
-        if length is None:                                               # the reference's empty forms pass through
-            save_result(result, out_dir, cls, scene_id)
-            continue
-        source = np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"))
-        target = np.load(os.path.join(target_dir, f"{scene_id}.npy"))
+        if length is None:
+            return None
+        source = _scene_cloud(cfg, scene_id)
+        target = np.load(os.path.join(cfg.get("lift_target_npy_dir"), f"{scene_id}.npy"))
         n_source, n_target = int(source.shape[0]), int(target.shape[0])
         if length != n_source:
             raise ValueError(f"{scene_id}: masks of {length} points for a source cloud of {n_source} points")
         inst = _saved_instances(result, n_source, device)
         if inst.rows is None:
-            save_result(result, out_dir, cls, scene_id)
-            continue
-        nn = lift.nearest(lift.nearest_index(source, radius, device), target)
-        lifted = lift.lift_instances(nn, inst, n_source, n_target)
-        ins = _lib.rows_to_rle(lifted.rows, n_target) if os.environ.get("BFF_SAVE_RLE") == "1" else \
-            _lib.unpack_rows(lifted.rows, n_target).cpu()
-        conf = lifted.conf.cpu() if torch.is_tensor(lifted.conf) else lifted.conf
-        save_result({"ins": ins, "conf": conf, "final_class": lifted.final_class}, out_dir, cls, scene_id)
-    return 0
+            return None
+        nn = lift.nearest(lift.nearest_index(source, lift.lift_max_dist(cfg), device), target)
+        return lift.lift_instances(nn, inst, n_source, n_target), n_target     # the rows keep their order: no `parent`
+
+    return _stage_main(_lift_parser(), argv, ("lift_output_dir", "lift_target_npy_dir"), lift.lift_max_dist, scene)
 
 
 def _evaluation_parser():

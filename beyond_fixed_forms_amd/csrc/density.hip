@@ -1,8 +1,9 @@
 // 3-D instances clustered by density, DBSCAN with a deterministic border rule (include/bff_hip.h: bff_dbscan_*;
 // DESIGN.md section 7j).  An instance is a bit row over the cloud; its points are counted against their neighbours within
-// eps in the same row, the core points are joined by the lock-free union-find of the split (spatial.hip), every border
-// point follows its nearest core neighbour, and the tail of the split (bff_split_count, bff_split_emit with every point
-// its own cell) turns the clusters into bit rows.
+// eps in the same row, the core points are joined by the lock-free union-find of the split, every border point follows
+// its nearest core neighbour, and the tail of the split (bff_split_count, bff_split_emit with every point its own cell)
+// turns the clusters into bit rows.  The walk over a point's 27 cells, the element index and the forest's prefix, init
+// and flatten kernels are shared with spatial.hip and nearest.hip: cells.h.
 //
 // Data layout in HBM
 //   points   f64 [N][stride >= 3]   the cloud in the caller's point order (x, y, z first): the queries
@@ -20,68 +21,16 @@
 //                                   neighbour's cluster, noise -> -1
 // No [K][N] integer array exists: what is per (row, point) is a bit, what is per element is indexed by e.
 // Work shape: one wave per 64-bit word of a row, lane = point, in the caller's point order.
-#include <cmath>
-
-#include "rows.h"
+#include "cells.h"
 
 namespace bff {
 
-constexpr int64_t kDenAxis = 1ll << 21;                            // cells per axis (spatial.hip: kVoxAxis)
-
-struct DenIndex {
-    const double *cloud;
-    const int64_t *keys;
-    const int32_t *offs;
-    const int32_t *order;
-    int64_t n_voxels, n_source;
-    double lo[3], cell, eps2;
-};
-
-// The candidates of a point: the gathered points of the 27 cells around its cell, as nine contiguous ranges (the three
-// x-neighbours of a (q1, q2) pair are consecutive keys: nearest.hip).  fn(i) returns true to stop the walk.
-template <typename Fn>
-__device__ __forceinline__ void for_candidates(const DenIndex &ix, const double (&x)[3], Fn fn)
-{
-    int64_t q[3];
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        // bff_voxel_keys' operations; the cell is tested on the double, before any conversion (NaN fails the test)
-        const double f = floor((x[a] - ix.lo[a]) / ix.cell);
-        ok = ok && f >= 0.0 && f < (double)kDenAxis;
-        q[a] = ok ? (int64_t)f : 0;
-    }
-    if (!ok) return;
-    const int64_t x_lo = q[0] > 0 ? q[0] - 1 : 0, x_hi = q[0] + 1 < kDenAxis ? q[0] + 1 : kDenAxis - 1;
-    for (int d2 = -1; d2 <= 1; ++d2) {
-        const int64_t a2 = q[2] + d2;
-        if (a2 < 0 || a2 >= kDenAxis) continue;                     // the axis itself: the key must not wrap
-        for (int d1 = -1; d1 <= 1; ++d1) {
-            const int64_t a1 = q[1] + d1;
-            if (a1 < 0 || a1 >= kDenAxis) continue;
-            const int64_t base = (a1 << 21) + (a2 << 42), want = base + x_lo, last = base + x_hi;
-            int64_t a = 0, b = ix.n_voxels;                         // first position with keys[pos] >= want
-            while (a < b) {
-                const int64_t m = (a + b) >> 1;
-                if (ix.keys[m] < want) a = m + 1; else b = m;
-            }
-            b = a;
-            while (b < ix.n_voxels && b < a + 3 && ix.keys[b] <= last) ++b;
-            if (b == a) continue;
-            int64_t i = ix.offs[a], end = ix.offs[b];
-            i = i > 0 ? i : 0, end = end < ix.n_source ? end : ix.n_source;      // a bad offs entry reads nothing outside
-            for (; i < end; ++i)
-                if (fn(i)) return;
-        }
-    }
-}
-
 // d2 of the statement: every operation rounded (-ffp-contract=off); the squares make it symmetric in its two points
-__device__ __forceinline__ bool den_near(const DenIndex &ix, const double (&x)[3], int64_t i, double &d)
+__device__ __forceinline__ bool den_near(const CellIndex &ix, double eps2, const double (&x)[3], int64_t i, double &d)
 {
     const double dx = x[0] - ix.cloud[i * 3], dy = x[1] - ix.cloud[i * 3 + 1], dz = x[2] - ix.cloud[i * 3 + 2];
     d = (dx * dx + dy * dy) + dz * dz;
-    return d <= ix.eps2;
+    return d <= eps2;
 }
 
 // one thread per word of set: the row's word masked by the finite points and by N
@@ -95,25 +44,6 @@ __global__ __launch_bounds__(256) void dbscan_mask_kernel(const uint64_t *__rest
     const int64_t left = n_points - w * 64;
     const uint64_t tail = left >= 64 ? ~0ull : (left > 0 ? (1ull << left) - 1 : 0);
     set[g] = rows[k * nw + w] & finite[w] & tail;
-}
-
-// spatial.hip's split_prefix_kernel, a sibling with its own lines: one wave per row, 64 words a step
-__global__ __launch_bounds__(kWave) void dbscan_prefix_kernel(const uint64_t *__restrict__ set, int n_rows, int64_t vw,
-                                                               int32_t *__restrict__ prefix, int32_t *__restrict__ row_total)
-{
-    const int k = blockIdx.x, lane = lane_id();
-    if (k >= n_rows) return;
-    int carry = 0;
-    for (int64_t w0 = 0; w0 < vw; w0 += kWave) {
-        const int64_t w = w0 + lane;
-        const int c = w < vw ? popc64(set[(int64_t)k * vw + w]) : 0;
-        int incl = c;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) { const int up = __shfl_up(incl, d); if (lane >= d) incl += up; }
-        if (w < vw) prefix[(int64_t)k * vw + w] = carry + incl - c;
-        carry += __shfl(incl, kWave - 1);
-    }
-    if (lane == 0) row_total[k] = carry;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -157,7 +87,7 @@ __device__ __forceinline__ bool den_bit(const uint64_t *__restrict__ bits, int64
 // core: the count stops at min_samples (core is a threshold).  The row's bit is tested before the distance.
 __global__ __launch_bounds__(256) void dbscan_core_kernel(const uint64_t *__restrict__ set, int n_rows, int64_t vw,
                                                            int64_t n_points, const double *__restrict__ points, int64_t stride,
-                                                           DenIndex ix, int min_samples, uint64_t *__restrict__ core)
+                                                           CellIndex ix, double eps2, int min_samples, uint64_t *__restrict__ core)
 {
     DenWord dw;
     if (!den_word(set, n_rows, vw, n_points, points, stride, dw)) return;     // core was cleared: a zero word stays zero
@@ -165,7 +95,7 @@ __global__ __launch_bounds__(256) void dbscan_core_kernel(const uint64_t *__rest
     if (dw.on) {
         for_candidates(ix, dw.x, [&](int64_t i) {
             double d;
-            if (den_bit(set, vw, dw.k, n_points, ix.order[i]) && den_near(ix, dw.x, i, d)) ++count;
+            if (den_bit(set, vw, dw.k, n_points, ix.order[i]) && den_near(ix, eps2, dw.x, i, d)) ++count;
             return count >= min_samples;
         });
     }
@@ -173,71 +103,28 @@ __global__ __launch_bounds__(256) void dbscan_core_kernel(const uint64_t *__rest
     if (lane_id() == 0) core[(int64_t)dw.k * vw + dw.w] = votes;    // one writer per word
 }
 
-__device__ __forceinline__ int den_element(const uint64_t *__restrict__ set, const int32_t *__restrict__ prefix,
-                                           const int32_t *__restrict__ elem_offs, int64_t vw, int k, int64_t p)
-{
-    const int64_t i = (int64_t)k * vw + (p >> 6);
-    return elem_offs[k] + prefix[i] + popc64(set[i] & ((1ull << (p & 63)) - 1));
-}
-
-__global__ __launch_bounds__(256) void dbscan_init_kernel(int32_t *__restrict__ parent, int n)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) parent[i] = i;
-}
-
-// spatial.hip's split_union, a sibling with its own lines: the larger root hangs under the smaller, so the final root of
-// a cluster is its smallest core element whatever the interleaving
-__device__ __forceinline__ void den_union(int32_t *parent, int a, int b)
-{
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        int expected = a;
-        if (__hip_atomic_compare_exchange_strong(parent + a, &expected, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            return;
-    }
-}
-
 // every core point against its core neighbours of a smaller index (the relation is symmetric: the other half is theirs)
 __global__ __launch_bounds__(256) void dbscan_union_kernel(const uint64_t *__restrict__ set, const uint64_t *__restrict__ core,
                                                             const int32_t *__restrict__ prefix, const int32_t *__restrict__ elem_offs,
                                                             int n_rows, int64_t vw, int64_t n_points,
-                                                            const double *__restrict__ points, int64_t stride, DenIndex ix,
+                                                            const double *__restrict__ points, int64_t stride, CellIndex ix, double eps2,
                                                             int n_elems, int32_t *__restrict__ parent)
 {
     DenWord dw;
     if (!den_word(set, n_rows, vw, n_points, points, stride, dw)) return;
     if (!dw.on || !((core[(int64_t)dw.k * vw + dw.w] >> lane_id()) & 1)) return;
-    const int e = den_element(set, prefix, elem_offs, vw, dw.k, dw.p);
+    const int e = element_of(set, prefix, elem_offs, vw, dw.k, dw.p);
     if ((unsigned)e >= (unsigned)n_elems) return;                   // elem_offs of another call: nothing is followed
     for_candidates(ix, dw.x, [&](int64_t i) {
         const int32_t s = ix.order[i];
         double d;
         // core is a subset of set: the element below exists
-        if ((int64_t)s < dw.p && den_bit(core, vw, dw.k, n_points, s) && den_near(ix, dw.x, i, d)) {
-            const int e2 = den_element(set, prefix, elem_offs, vw, dw.k, s);
-            if ((unsigned)e2 < (unsigned)n_elems) den_union(parent, e, e2);
+        if ((int64_t)s < dw.p && den_bit(core, vw, dw.k, n_points, s) && den_near(ix, eps2, dw.x, i, d)) {
+            const int e2 = element_of(set, prefix, elem_offs, vw, dw.k, s);
+            if ((unsigned)e2 < (unsigned)n_elems) uf_union(parent, e, e2);
         }
         return false;
     });
-}
-
-// After the unions (a kernel boundary): every element points at its root.  The walk only reads (spatial.hip,
-// split_flatten_kernel: uf_find's path halving must not be used here).
-__global__ __launch_bounds__(256) void dbscan_flatten_kernel(int32_t *__restrict__ parent, int n)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int x = i, p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) {
-        x = p;
-        p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (x != i) __hip_atomic_store(parent + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // After the flatten (a kernel boundary).  A non-core element takes the root of its nearest core neighbour (equal d2 to
@@ -246,27 +133,27 @@ __global__ __launch_bounds__(256) void dbscan_flatten_kernel(int32_t *__restrict
 __global__ __launch_bounds__(256) void dbscan_border_kernel(const uint64_t *__restrict__ set, const uint64_t *__restrict__ core,
                                                              const int32_t *__restrict__ prefix, const int32_t *__restrict__ elem_offs,
                                                              int n_rows, int64_t vw, int64_t n_points,
-                                                             const double *__restrict__ points, int64_t stride, DenIndex ix,
+                                                             const double *__restrict__ points, int64_t stride, CellIndex ix, double eps2,
                                                              int n_elems, int32_t *parent)
 {
     DenWord dw;
     if (!den_word(set, n_rows, vw, n_points, points, stride, dw)) return;
     if (!dw.on || ((core[(int64_t)dw.k * vw + dw.w] >> lane_id()) & 1)) return;
-    const int e = den_element(set, prefix, elem_offs, vw, dw.k, dw.p);
+    const int e = element_of(set, prefix, elem_offs, vw, dw.k, dw.p);
     if ((unsigned)e >= (unsigned)n_elems) return;
     double best = INFINITY;
     int32_t best_s = -1;
     for_candidates(ix, dw.x, [&](int64_t i) {
         const int32_t s = ix.order[i];
         double d;
-        if (den_bit(core, vw, dw.k, n_points, s) && den_near(ix, dw.x, i, d) &&
+        if (den_bit(core, vw, dw.k, n_points, s) && den_near(ix, eps2, dw.x, i, d) &&
             (d < best || (d == best && (best_s < 0 || s < best_s))))
             best = d, best_s = s;
         return false;
     });
     int root = -1;
     if (best_s >= 0) {
-        const int e2 = den_element(set, prefix, elem_offs, vw, dw.k, best_s);
+        const int e2 = element_of(set, prefix, elem_offs, vw, dw.k, best_s);
         if ((unsigned)e2 < (unsigned)n_elems) root = parent[e2];
     }
     parent[e] = root;
@@ -279,21 +166,6 @@ static int den_sizes(const char *what, int32_t n_rows, int64_t n_points)
     // every element is a set bit of `set`: its index stays below 2^31
     BFF_LIMIT((int64_t)n_rows * ceil_div(n_points, 64) * 64 < (1ll << 31), "%s: n_rows x n_points = %lld x %lld, at most 2^31 - 1 bits",
               what, (long long)n_rows, (long long)n_points);
-    return BFF_OK;
-}
-
-// the index's arguments, checked and gathered; n_voxels > 0
-static int den_index(const char *what, const double *cloud, const int64_t *keys, const int32_t *offs, const int32_t *order,
-                     int64_t n_voxels, int64_t n_source, const double *lo_host, double cell, double eps, DenIndex &ix)
-{
-    BFF_REQUIRE(cloud && keys && offs && order && lo_host, "%s: null pointer (cloud, keys, offs, order, lo_host)", what);
-    ix.cloud = cloud, ix.keys = keys, ix.offs = offs, ix.order = order, ix.n_voxels = n_voxels, ix.n_source = n_source;
-    for (int a = 0; a < 3; ++a) {
-        ix.lo[a] = lo_host[a];
-        BFF_REQUIRE(std::isfinite(ix.lo[a]), "%s: lo_host: the grid's minimum is not finite", what);
-    }
-    ix.cell = cell;
-    ix.eps2 = eps * eps;
     return BFF_OK;
 }
 
@@ -329,7 +201,7 @@ extern "C" int bff_dbscan_elements(const uint64_t *rows, int32_t n_rows, int64_t
     hipStream_t st = as_stream(stream);
     const int64_t vw = ceil_div(n_points, 64);
     dbscan_mask_kernel<<<(unsigned)ceil_div((int64_t)n_rows * vw, 256), 256, 0, st>>>(rows, n_rows, nw, n_points, finite, vw, set);
-    dbscan_prefix_kernel<<<(unsigned)n_rows, kWave, 0, st>>>(set, n_rows, vw, prefix, row_total);
+    elements_prefix(set, n_rows, vw, prefix, row_total, st);
     return launched("bff_dbscan_elements");
 }
 
@@ -344,18 +216,16 @@ extern "C" int bff_dbscan_core(const uint64_t *set, int32_t n_rows, int64_t n_po
     BFF_REQUIRE(min_samples >= 1, "bff_dbscan_core: min_samples must be >= 1");
     if (n_rows == 0 || n_points == 0) return BFF_OK;
     BFF_REQUIRE(core, "bff_dbscan_core: null pointer (core)");
-    DenIndex ix;
-    if (n_voxels > 0) {
-        BFF_REQUIRE(set && points, "bff_dbscan_core: null pointer (set, points)");
-        rc = den_index("bff_dbscan_core", cloud, keys, offs, order, n_voxels, n_source, lo_host, cell, eps, ix);
-        if (rc != BFF_OK) return rc;
-    }
+    BFF_REQUIRE(n_voxels == 0 || (set && points), "bff_dbscan_core: null pointer (set, points)");
+    CellIndex ix;
+    rc = cell_index("bff_dbscan_core", cloud, keys, offs, order, n_voxels, n_source, lo_host, cell, ix);
+    if (rc != BFF_OK) return rc;
     hipStream_t st = as_stream(stream);
     const int64_t vw = ceil_div(n_points, 64);
     hipError_t e = hipMemsetAsync(core, 0, sizeof(uint64_t) * (size_t)n_rows * (size_t)vw, st);
     if (e != hipSuccess) return fail((int)e, "bff_dbscan_core: memset: %s", hipGetErrorString(e));
     if (n_voxels == 0) return BFF_OK;                               // no finite point: no element
-    dbscan_core_kernel<<<den_word_blocks(n_rows, vw), 256, 0, st>>>(set, n_rows, vw, n_points, points, stride, ix, min_samples, core);
+    dbscan_core_kernel<<<den_word_blocks(n_rows, vw), 256, 0, st>>>(set, n_rows, vw, n_points, points, stride, ix, eps * eps, min_samples, core);
     return launched("bff_dbscan_core");
 }
 
@@ -372,15 +242,15 @@ extern "C" int bff_dbscan_link(const uint64_t *set, const uint64_t *core, const 
     if (n_rows == 0 || n_points == 0 || n_elems == 0 || n_voxels == 0) return BFF_OK;
     BFF_REQUIRE(parent, "bff_dbscan_link: null pointer (parent)");
     BFF_REQUIRE(set && core && prefix && elem_offs && points, "bff_dbscan_link: null pointer (set, core, prefix, elem_offs, points)");
-    DenIndex ix;
-    rc = den_index("bff_dbscan_link", cloud, keys, offs, order, n_voxels, n_source, lo_host, cell, eps, ix);
+    CellIndex ix;
+    rc = cell_index("bff_dbscan_link", cloud, keys, offs, order, n_voxels, n_source, lo_host, cell, ix);
     if (rc != BFF_OK) return rc;
     hipStream_t st = as_stream(stream);
     const int64_t vw = ceil_div(n_points, 64);
-    const unsigned eb = (unsigned)ceil_div(n_elems, 256), wb = den_word_blocks(n_rows, vw);
-    dbscan_init_kernel<<<eb, 256, 0, st>>>(parent, n_elems);
-    dbscan_union_kernel<<<wb, 256, 0, st>>>(set, core, prefix, elem_offs, n_rows, vw, n_points, points, stride, ix, n_elems, parent);
-    dbscan_flatten_kernel<<<eb, 256, 0, st>>>(parent, n_elems);
-    dbscan_border_kernel<<<wb, 256, 0, st>>>(set, core, prefix, elem_offs, n_rows, vw, n_points, points, stride, ix, n_elems, parent);
+    const unsigned wb = den_word_blocks(n_rows, vw);
+    forest_init(parent, n_elems, st);
+    dbscan_union_kernel<<<wb, 256, 0, st>>>(set, core, prefix, elem_offs, n_rows, vw, n_points, points, stride, ix, eps * eps, n_elems, parent);
+    forest_flatten(parent, n_elems, st);
+    dbscan_border_kernel<<<wb, 256, 0, st>>>(set, core, prefix, elem_offs, n_rows, vw, n_points, points, stride, ix, eps * eps, n_elems, parent);
     return launched("bff_dbscan_link");
 }

@@ -375,21 +375,7 @@ __global__ __launch_bounds__(256) void merge_adjacency_kernel(const uint64_t *__
 }
 
 // ---- components without an adjacency matrix: union-find in the tile epilogue -----------------------
-// The forest and uf_find: rows.h.
-__device__ __forceinline__ void uf_union(int32_t *parent, int a, int b)
-{
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }            // a > b: hang the larger root under the smaller
-        int expected = a;
-        if (__hip_atomic_compare_exchange_strong(parent + a, &expected, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            return;
-    }
-}
-
+// The forest, uf_find and uf_union: rows.h.
 __global__ void uf_init_kernel(int32_t *parent, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

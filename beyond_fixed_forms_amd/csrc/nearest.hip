@@ -1,6 +1,6 @@
 // 3-D instances lifted from a subsampled cloud to the full cloud (include/bff_hip.h: bff_nn_search, bff_rows_to_columns,
 // bff_lift_bits).  A nearest-neighbour search on the voxel grid of section 7g, and a many-row bit
-// gather that takes "no source" for an answer.
+// gather that takes "no source" for an answer.  The walk over a query's 27 cells is cells.h's, shared with density.hip.
 //
 // Data layout in HBM
 //   src      f64 [M'][3]            the source points that have a cell, gathered into (cell, point index) order: the
@@ -13,70 +13,31 @@
 //   cols     u64 [M][kw]            kw = ceil(K / 64): bit k of cols[s] = bit s of row k (the rows transposed)
 //   rows_out u64 [K][ceil(N / 64)]  bit p of row k = bit nn[p] of input row k, 0 where nn[p] is not in [0, M)
 // No atomics, no LDS: every output word has one writer and every result is the same on every run.
-#include <cmath>
-
-#include "rows.h"
+#include "cells.h"
 
 namespace bff {
 
-constexpr int64_t kNnAxis = 1ll << 21;                             // cells per axis (spatial.hip: kVoxAxis)
 constexpr int kLiftWaves = 4;                                      // waves per block of the transpose and the gather
 
-struct NnFrame { double lo[3]; double cell; double r2; };
-
-// One lane per query.  The three x-neighbours of a (q1, q2) pair are consecutive keys, so one lower-bound search and a
-// walk over at most three entries of `keys` give one contiguous candidate range: 9 searches, not 27.
-__global__ __launch_bounds__(256) void nn_search_kernel(const double *__restrict__ src, const int64_t *__restrict__ keys,
-                                                         const int32_t *__restrict__ offs, const int32_t *__restrict__ order,
-                                                         int64_t n_voxels, int64_t n_source, NnFrame fr,
-                                                         const double *__restrict__ queries,
-                                                         int64_t n, int64_t stride, int32_t *__restrict__ nn,
-                                                         double *__restrict__ d2_out)
+// One lane per query: the nearest of its candidates (cells.h: for_candidates) within the radius.
+__global__ __launch_bounds__(256) void nn_search_kernel(CellIndex ix, double r2, const double *__restrict__ queries, int64_t n,
+                                                         int64_t stride, int32_t *__restrict__ nn, double *__restrict__ d2_out)
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     const double x[3] = {queries[p * stride], queries[p * stride + 1], queries[p * stride + 2]};
-    int64_t q[3];
-    bool ok = isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        // bff_voxel_keys' operations; the cell is tested on the double, before any conversion (NaN fails the test)
-        const double f = floor((x[a] - fr.lo[a]) / fr.cell);
-        ok = ok && f >= -1.0 && f <= (double)kNnAxis;
-        q[a] = ok ? (int64_t)f : 0;
-    }
     double best = INFINITY;
     int32_t best_s = -1;
-    if (ok) {
-        const int64_t x_lo = q[0] > 0 ? q[0] - 1 : 0, x_hi = q[0] + 1 < kNnAxis ? q[0] + 1 : kNnAxis - 1;
-        for (int d2 = -1; d2 <= 1; ++d2) {
-            const int64_t a2 = q[2] + d2;
-            if (a2 < 0 || a2 >= kNnAxis) continue;                  // the axis itself: the key must not wrap
-            for (int d1 = -1; d1 <= 1; ++d1) {
-                const int64_t a1 = q[1] + d1;
-                if (a1 < 0 || a1 >= kNnAxis) continue;
-                const int64_t base = (a1 << 21) + (a2 << 42), want = base + x_lo, last = base + x_hi;
-                int64_t a = 0, b = n_voxels;                        // first position with keys[pos] >= want
-                while (a < b) {
-                    const int64_t m = (a + b) >> 1;
-                    if (keys[m] < want) a = m + 1; else b = m;
-                }
-                b = a;
-                while (b < n_voxels && b < a + 3 && keys[b] <= last) ++b;
-                if (b == a) continue;
-                int64_t i = offs[a], end = offs[b];
-                i = i > 0 ? i : 0, end = end < n_source ? end : n_source;       // a bad offs entry reads nothing outside src
-                for (; i < end; ++i) {
-                    const double dx = x[0] - src[i * 3], dy = x[1] - src[i * 3 + 1], dz = x[2] - src[i * 3 + 2];
-                    const double d = (dx * dx + dy * dy) + dz * dz;  // every operation rounded: -ffp-contract=off
-                    if (!(d <= fr.r2)) continue;
-                    const int32_t s = order[i];
-                    // the nine ranges are not in index order: the tie goes to the smallest index explicitly
-                    if (d < best || (d == best && (best_s < 0 || s < best_s))) best = d, best_s = s;
-                }
-            }
+    for_candidates(ix, x, [&](int64_t i) {
+        const double dx = x[0] - ix.cloud[i * 3], dy = x[1] - ix.cloud[i * 3 + 1], dz = x[2] - ix.cloud[i * 3 + 2];
+        const double d = (dx * dx + dy * dy) + dz * dz;              // every operation rounded: -ffp-contract=off
+        if (d <= r2) {
+            const int32_t s = ix.order[i];
+            // the nine ranges are not in index order: the tie goes to the smallest index explicitly
+            if (d < best || (d == best && (best_s < 0 || s < best_s))) best = d, best_s = s;
         }
-    }
+        return false;
+    });
     nn[p] = best_s;
     if (d2_out) d2_out[p] = best;
 }
@@ -149,19 +110,11 @@ extern "C" int bff_nn_search(const double *src, const int64_t *keys, const int32
     if (n_queries == 0) return BFF_OK;
     BFF_REQUIRE(queries, "bff_nn_search: null pointer (queries)");
     BFF_REQUIRE(nn, "bff_nn_search: null pointer (nn)");
-    BFF_REQUIRE(n_voxels == 0 || lo_host, "bff_nn_search: null pointer (lo_host)");
-    BFF_REQUIRE(n_voxels == 0 || keys, "bff_nn_search: null pointer (keys)");
-    BFF_REQUIRE(n_voxels == 0 || offs, "bff_nn_search: null pointer (offs)");
-    BFF_REQUIRE(n_voxels == 0 || (src && order), "bff_nn_search: null pointer (src, order)");
-    NnFrame fr;
-    for (int a = 0; a < 3; ++a) {
-        fr.lo[a] = n_voxels ? lo_host[a] : 0.0;
-        BFF_REQUIRE(std::isfinite(fr.lo[a]), "bff_nn_search: lo_host: the grid's minimum is not finite");
-    }
-    fr.cell = cell;
-    fr.r2 = radius * radius;
-    nn_search_kernel<<<(unsigned)ceil_div(n_queries, 256), 256, 0, as_stream(stream)>>>(src, keys, offs, order, n_voxels, n_source,
-                                                                                       fr, queries, n_queries, stride, nn, d2);
+    CellIndex ix;
+    const int rc = cell_index("bff_nn_search", src, keys, offs, order, n_voxels, n_source, lo_host, cell, ix);
+    if (rc != BFF_OK) return rc;
+    nn_search_kernel<<<(unsigned)ceil_div(n_queries, 256), 256, 0, as_stream(stream)>>>(ix, radius * radius, queries, n_queries,
+                                                                                       stride, nn, d2);
     return launched("bff_nn_search");
 }
 

@@ -1,4 +1,5 @@
-// Shared by the bit-row units: what more than one of rows.hip, merge.hip, groups.hip and scene.hip needs.
+// Shared by the bit-row units: what more than one of rows.hip, merge.hip, groups.hip, scene.hip and the 3-D stages
+// (cells.h) needs.
 // Anything a single unit uses stays in that unit.
 #pragma once
 
@@ -28,6 +29,22 @@ __device__ __forceinline__ int uf_find(int32_t *parent, int x)
         p = g;
     }
     return x;
+}
+
+// The larger root hangs under the smaller, so the final root of a component is its smallest member whatever the
+// interleaving.  merge.hip's tile epilogue, and the element forests of spatial.hip and density.hip (cells.h).
+__device__ __forceinline__ void uf_union(int32_t *parent, int a, int b)
+{
+    for (;;) {
+        a = uf_find(parent, a);
+        b = uf_find(parent, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }            // a > b: hang the larger root under the smaller
+        int expected = a;
+        if (__hip_atomic_compare_exchange_strong(parent + a, &expected, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT))
+            return;
+    }
 }
 
 // bff_merge_components with the tile pass on a stream of its own (`heavy`; bff_scene_project keeps the chip-filling

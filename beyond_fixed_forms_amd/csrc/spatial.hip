@@ -1,6 +1,8 @@
 // 3-D instances split into spatially connected parts (include/bff_hip.h: bff_voxel_*, bff_split_*).
 // An instance is a bit row over the cloud; here its points are binned into the cells of a voxel grid, cells that touch
 // (26-adjacency) are joined by a lock-free union-find, and every component becomes a bit row of its own.
+// What nearest.hip and density.hip share with this unit is in cells.h: the cell of a point, the search over `keys`, the
+// element index; the forest's prefix, init and flatten kernels are defined here and launched by density.hip as well.
 //
 // Data layout in HBM
 //   points   f64 [N][stride >= 3]   the cloud in the caller's point order (x, y, z first)
@@ -18,13 +20,10 @@
 //   table    i32 [T]                root element -> output row, or -1
 //   out      u64 [R][nw]            the parts
 // No [K][V] or [K][N] integer array exists: what is per (row, cell) is a bit, what is per element is indexed by e.
-#include <cmath>
-
-#include "rows.h"
+#include "cells.h"
 
 namespace bff {
 
-constexpr int64_t kVoxAxis = 1ll << 21;                            // cells per axis
 constexpr int64_t kVoxNoKey = 0x7fffffffffffffffll;               // sorts after every key (keys are < 2^63)
 constexpr int kVoxNbr = 13;
 
@@ -69,7 +68,7 @@ __global__ __launch_bounds__(256) void voxel_bounds_kernel(const double *__restr
 
 struct VoxelFrame { double lo[3]; double cell; };
 
-// q = floor((x - lo) / c): IEEE subtraction, IEEE division, floor (the unit is compiled with -ffp-contract=off)
+// the key of every point's cell (cells.h: cell_coord)
 __global__ __launch_bounds__(256) void voxel_keys_kernel(const double *__restrict__ points, int64_t n, int64_t stride,
                                                           VoxelFrame fr, int64_t *__restrict__ key)
 {
@@ -81,10 +80,10 @@ __global__ __launch_bounds__(256) void voxel_keys_kernel(const double *__restric
         k = 0;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const double q = floor((x[a] - fr.lo[a]) / fr.cell);
+            const double q = cell_coord(x[a], fr.lo[a], fr.cell);
             // 0 <= q < 2^21 for a box that holds the point (checked by the entry point); anything else has no cell
-            if (!(q >= 0.0 && q < (double)kVoxAxis)) { k = kVoxNoKey; break; }
-            k += (int64_t)q << (21 * a);
+            if (!(q >= 0.0 && q < (double)kCellAxis)) { k = kVoxNoKey; break; }
+            k += (int64_t)q << (kCellBits * a);
         }
     }
     key[p] = k;
@@ -136,17 +135,13 @@ __global__ __launch_bounds__(256) void voxel_neighbours_kernel(const int64_t *__
     bool inside = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const int64_t q = ((k >> (21 * a)) & (kVoxAxis - 1)) + d[a];
-        inside = inside && q >= 0 && q < kVoxAxis;                  // the axis itself: the key must not wrap
-        want += q << (21 * a);
+        const int64_t q = ((k >> (kCellBits * a)) & (kCellAxis - 1)) + d[a];
+        inside = inside && q >= 0 && q < kCellAxis;                 // the axis itself: the key must not wrap
+        want += q << (kCellBits * a);
     }
     int32_t found = -1;
     if (inside) {
-        int64_t a = 0, b = n_voxels;                                // first position with keys[pos] >= want
-        while (a < b) {
-            const int64_t m = (a + b) >> 1;
-            if (keys[m] < want) a = m + 1; else b = m;
-        }
+        const int64_t a = keys_lower_bound(keys, n_voxels, want);
         if (a < n_voxels && keys[a] == want) found = (int32_t)a;
     }
     nbr[t] = found;
@@ -192,8 +187,9 @@ __global__ __launch_bounds__(256) void split_occupancy_kernel(const uint64_t *__
         atomicOr(occ + (int64_t)rw.k * vw + (rw.v >> 6), 1ull << (rw.v & 63));      // result unused: returnless
 }
 
-// one wave per row: the exclusive prefix of the words' popcounts, 64 words a step with the carry in a register
-__global__ __launch_bounds__(kWave) void split_prefix_kernel(const uint64_t *__restrict__ occ, int n_rows, int64_t vw,
+// one wave per row of a [K][vw] bit array: the exclusive prefix of the words' popcounts, 64 words a step with the carry
+// in a register
+__global__ __launch_bounds__(kWave) void elements_prefix_kernel(const uint64_t *__restrict__ occ, int n_rows, int64_t vw,
                                                               int32_t *__restrict__ prefix, int32_t *__restrict__ row_total)
 {
     const int k = blockIdx.x, lane = lane_id();
@@ -211,34 +207,10 @@ __global__ __launch_bounds__(kWave) void split_prefix_kernel(const uint64_t *__r
     if (lane == 0) row_total[k] = carry;
 }
 
-// the element of (row k, cell v); the cell's bit is set in occ
-__device__ __forceinline__ int element_of(const uint64_t *__restrict__ occ, const int32_t *__restrict__ prefix,
-                                          const int32_t *__restrict__ elem_offs, int64_t vw, int k, int32_t v)
-{
-    const int64_t i = (int64_t)k * vw + (v >> 6);
-    return elem_offs[k] + prefix[i] + popc64(occ[i] & ((1ull << (v & 63)) - 1));
-}
-
-__global__ __launch_bounds__(256) void split_init_kernel(int32_t *__restrict__ parent, int n)
+__global__ __launch_bounds__(256) void forest_init_kernel(int32_t *__restrict__ parent, int n)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) parent[i] = i;
-}
-
-// merge.hip's uf_union, a sibling with its own lines (that unit keeps its machine code): the larger root hangs under the
-// smaller, so the final root of a component is its smallest element whatever the interleaving
-__device__ __forceinline__ void split_union(int32_t *parent, int a, int b)
-{
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        int expected = a;
-        if (__hip_atomic_compare_exchange_strong(parent + a, &expected, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            return;
-    }
 }
 
 // one thread per occ word: every set bit against its 13 forward neighbours in the same row
@@ -267,7 +239,7 @@ __global__ __launch_bounds__(256) void split_union_kernel(const uint64_t *__rest
             if (u < 0 || u >= n_voxels) continue;
             if (!((occ[(int64_t)k * vw + (u >> 6)] >> (u & 63)) & 1)) continue;
             const int e2 = element_of(occ, prefix, elem_offs, vw, k, u);
-            if ((unsigned)e2 < (unsigned)n_elems) split_union(parent, e, e2);
+            if ((unsigned)e2 < (unsigned)n_elems) uf_union(parent, e, e2);
         }
     }
 }
@@ -275,7 +247,7 @@ __global__ __launch_bounds__(256) void split_union_kernel(const uint64_t *__rest
 // After the unions (a kernel boundary): every element points at its root.  The walk only reads -- uf_find's path halving
 // would let another thread's late store of a grandparent land on top of this thread's root -- so the only stores of this
 // kernel are roots, and every parent[] a walk meets is still an ancestor.
-__global__ __launch_bounds__(256) void split_flatten_kernel(int32_t *__restrict__ parent, int n)
+__global__ __launch_bounds__(256) void forest_flatten_kernel(int32_t *__restrict__ parent, int n)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -377,6 +349,21 @@ static int split_check(const char *what, int32_t n_rows, int64_t nw, int64_t n_p
 
 static unsigned row_word_blocks(int32_t n_rows, int64_t nw) { return (unsigned)ceil_div((int64_t)n_rows * nw, 256 / kWave); }
 
+void elements_prefix(const uint64_t *bits, int32_t n_rows, int64_t vw, int32_t *prefix, int32_t *row_total, hipStream_t st)
+{
+    elements_prefix_kernel<<<(unsigned)n_rows, kWave, 0, st>>>(bits, n_rows, vw, prefix, row_total);
+}
+
+void forest_init(int32_t *parent, int32_t n_elems, hipStream_t st)
+{
+    forest_init_kernel<<<(unsigned)ceil_div(n_elems, 256), 256, 0, st>>>(parent, n_elems);
+}
+
+void forest_flatten(int32_t *parent, int32_t n_elems, hipStream_t st)
+{
+    forest_flatten_kernel<<<(unsigned)ceil_div(n_elems, 256), 256, 0, st>>>(parent, n_elems);
+}
+
 }  // namespace bff
 
 using namespace bff;
@@ -411,8 +398,8 @@ extern "C" int bff_voxel_keys(const double *points, int64_t n_points, int64_t st
         BFF_REQUIRE(std::isfinite(lo_host[a]) && std::isfinite(hi_host[a]) && lo_host[a] <= hi_host[a],
                     "bff_voxel_keys: the box must be finite and ordered");
         // subtraction, division and floor are monotonic: no point of the box has a larger q than its far corner
-        const double q = std::floor((hi_host[a] - lo_host[a]) / cell);
-        BFF_LIMIT(q < (double)kVoxAxis, "bff_voxel_keys: %g cells on axis %d, at most 2^21 (a larger cell is needed)", q, a);
+        const double q = cell_coord(hi_host[a], lo_host[a], cell);
+        BFF_LIMIT(q < (double)kCellAxis, "bff_voxel_keys: %g cells on axis %d, at most 2^21 (a larger cell is needed)", q, a);
         fr.lo[a] = lo_host[a];
     }
     BFF_REQUIRE(points && key, "bff_voxel_keys: null pointer");
@@ -469,7 +456,7 @@ extern "C" int bff_split_occupancy(const uint64_t *rows, int32_t n_rows, int64_t
         rc = launched("bff_split_occupancy");
         if (rc != BFF_OK) return rc;
     }
-    split_prefix_kernel<<<(unsigned)n_rows, kWave, 0, st>>>(occ, n_rows, vw, prefix, row_total);
+    elements_prefix(occ, n_rows, vw, prefix, row_total, st);
     return launched("bff_split_occupancy");
 }
 
@@ -483,11 +470,10 @@ extern "C" int bff_split_union(const uint64_t *occ, const int32_t *prefix, const
     BFF_REQUIRE(occ && prefix && elem_offs && nbr && parent, "bff_split_union: null pointer");
     hipStream_t st = as_stream(stream);
     const int64_t vw = ceil_div(n_voxels, 64);
-    const unsigned eb = (unsigned)ceil_div(n_elems, 256);
-    split_init_kernel<<<eb, 256, 0, st>>>(parent, n_elems);
+    forest_init(parent, n_elems, st);
     split_union_kernel<<<(unsigned)ceil_div((int64_t)n_rows * vw, 256), 256, 0, st>>>(occ, prefix, elem_offs, n_rows, vw, n_voxels,
                                                                                       nbr, n_elems, parent);
-    split_flatten_kernel<<<eb, 256, 0, st>>>(parent, n_elems);
+    forest_flatten(parent, n_elems, st);
     return launched("bff_split_union");
 }
 

@@ -22,7 +22,7 @@ import dataclasses
 import numpy as np
 import torch
 
-from . import _lib, spatial, superpoints
+from . import _lib, instances3d, spatial, superpoints
 from ._lib import _ptr, call, f64, i32, i64
 
 
@@ -36,55 +36,26 @@ class NearestIndex:
     cloud: torch.Tensor            # float64 [M'][3] (device): source_points[order]
 
 
-def _number(name, x):
-    if isinstance(x, bool) or not isinstance(x, (int, float)) or not (float(x) > 0.0 and np.isfinite(float(x))):
-        raise ValueError(f"{name} must be a finite number of metres > 0, got {x!r}")
-    return float(x)
-
-
 def subsample_voxel(cfg) -> float:
-    v = cfg.get("subsample_voxel")
-    if v is None:
-        raise ValueError("subsample_voxel is not set in the config (metres, > 0)")
-    return _number("subsample_voxel", v)
+    return instances3d.config_metres(cfg, "subsample_voxel")
 
 
 def lift_max_dist(cfg) -> float:
     """Absent: 2 x subsample_voxel (every finite point of the cloud the subsample was taken from has a source once the
     radius reaches sqrt(3) x subsample_voxel)."""
-    r = cfg.get("lift_max_dist")
-    if r is None:
+    if cfg.get("lift_max_dist") is None:
         if cfg.get("subsample_voxel") is None:
             raise ValueError("lift_max_dist is not set in the config, and neither is subsample_voxel (metres, > 0)")
         return 2.0 * subsample_voxel(cfg)
-    return _number("lift_max_dist", r)
-
-
-def _device_points(what, points, device):
-    """-> float64 [N][>= 3] on the device, contiguous."""
-    if torch.is_tensor(points):
-        if not points.is_cuda:
-            raise ValueError(f"{what} takes an array or a device tensor (no CPU path)")
-        if points.dtype != f64 or points.dim() != 2 or points.shape[1] < 3:
-            raise TypeError(f"{what}: float64 [N][>= 3] points expected")
-        return points.contiguous()
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError(f"{what} needs a GPU device (no CPU path)")
-    a = np.asarray(points)
-    if a.ndim != 2 or a.shape[1] < 3:
-        raise TypeError(f"{what}: an (N, >= 3) array expected, got {a.shape}")
-    return torch.as_tensor(np.ascontiguousarray(a[:, :3], dtype=np.float64)).to(dev)
+    return instances3d.config_metres(cfg, "lift_max_dist")
 
 
 def subsample(points, voxel, device="cuda") -> torch.Tensor:
     """points: the (N, >= 3) array of <scene>.npy, or a float64 device tensor of that shape.  -> sample int32 [V] on the
     device: the smallest point index of every occupied cell of spatial.voxel_grid(points, voxel), in ascending point
     index.  A non-finite point has no cell and is never sampled."""
-    voxel = float(voxel)
-    if not (voxel > 0.0 and np.isfinite(voxel)):
-        raise ValueError(f"subsample: voxel must be a finite number of metres > 0, got {voxel!r}")
-    pts = _device_points("subsample", points, device)
+    voxel = instances3d.metres("subsample: voxel", voxel)
+    pts = instances3d.device_points("subsample", points, device)
     grid = spatial.voxel_grid(pts, voxel)
     dev, n, v = pts.device, grid.n_points, grid.n_voxels
     if v == 0:
@@ -102,10 +73,8 @@ def subsample(points, voxel, device="cuda") -> torch.Tensor:
 def nearest_index(source_points, max_dist, device="cuda") -> NearestIndex:
     """source_points: an (M, >= 3) array or a float64 device tensor of that shape; max_dist: metres, > 0 and finite.  The
     index serves every query set."""
-    r = float(max_dist)
-    if not (r > 0.0 and np.isfinite(r)):
-        raise ValueError(f"nearest_index: max_dist must be a finite number of metres > 0, got {max_dist!r}")
-    pts = _device_points("nearest_index", source_points, device)
+    r = instances3d.metres("nearest_index: max_dist", max_dist)
+    pts = instances3d.device_points("nearest_index", source_points, device)
     grid = spatial.voxel_grid(pts, r)
     cells = superpoints.superpoints_from_grid(grid)                           # the cells' point lists, ascending index
     with torch.cuda.device(pts.device):
@@ -118,7 +87,7 @@ def nearest(index: NearestIndex, query_points, return_d2=False):
     nearest source point within the index's max_dist, a tie to the smallest index, -1 = none), with return_d2 also
     d2 float64 [N] (the squared distance, +inf = none)."""
     dev = index.cloud.device
-    q = _device_points("nearest", query_points, dev)
+    q = instances3d.device_points("nearest", query_points, dev)
     if q.device != dev:
         raise ValueError("nearest: the queries and the index live on different devices")
     n, v, grid = int(q.shape[0]), index.grid.n_voxels, index.grid
@@ -167,14 +136,7 @@ def lift_instances(nn, result, n_source, n_target):
     source cloud, `conf`, `final_class`).  -> the same kind with `rows` replaced by the rows over the target cloud; `conf`,
     `final_class`, the row count and the order are untouched, rows that end up empty included (`n_points`, where the result
     has it, becomes n_target).  A result whose rows is None comes back as it is."""
-    import copy
     rows = getattr(result, "rows", None)
     if rows is None:
         return result
-    new = copy.copy(result)
-    new.rows = lift_rows(nn, rows, n_source, n_target)
-    if hasattr(result, "n_points"):                                         # to_dict() unpacks to the target's length
-        new.n_points = int(n_target)
-    if getattr(result, "prefetch", None) is not None:                       # a Stage2Result's refinement inputs: of the
-        new.prefetch = None                                                 # source cloud's rows
-    return new
+    return instances3d.replace_rows(result, lift_rows(nn, rows, n_source, n_target), n_points=n_target)

@@ -20,12 +20,12 @@ import dataclasses
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, instances3d
 from ._lib import _ptr, call, i32, i64
+from .instances3d import KEPT_FIRST_READ, _take  # noqa: F401  (importable under their names here)
 
 MAX_AXIS_CELLS = 1 << 21
 MODES = ("split", "largest")
-KEPT_FIRST_READ = 1 << 16          # kept components the second read-back of a split call fetches with their count
 
 
 @dataclasses.dataclass
@@ -53,23 +53,8 @@ def _decode_box(box):
 def voxel_grid(points, cell, device="cuda") -> VoxelGrid:
     """points: the (N, >= 3) array of <scene>.npy (x, y, z first), or a float64 device tensor of that shape.  cell: metres,
     > 0 and finite.  Two read-backs (the box, the number of cells); the grid serves every class and call of the scene."""
-    cell = float(cell)
-    if not (cell > 0.0 and np.isfinite(cell)):
-        raise ValueError(f"voxel_grid: cell must be a finite number of metres > 0, got {cell!r}")
-    if torch.is_tensor(points):
-        if not points.is_cuda:
-            raise ValueError("voxel_grid takes an array or a device tensor (no CPU path)")
-        if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] < 3:
-            raise TypeError("voxel_grid: float64 [N][>= 3] points expected")
-        pts = points.contiguous()
-    else:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("voxel_grid needs a GPU device (no CPU path)")
-        a = np.asarray(points)
-        if a.ndim != 2 or a.shape[1] < 3:
-            raise TypeError(f"voxel_grid: an (N, >= 3) array expected, got {a.shape}")
-        pts = torch.as_tensor(np.ascontiguousarray(a[:, :3], dtype=np.float64)).to(dev)
+    cell = instances3d.metres("voxel_grid: cell", cell)
+    pts = instances3d.device_points("voxel_grid", points, device)
     dev, n, stride = pts.device, int(pts.shape[0]), int(pts.shape[1])
     with torch.cuda.device(dev):
         empty = lambda: VoxelGrid(cell, np.full(3, np.nan), n, 0, torch.full((n,), -1, dtype=i32, device=dev),
@@ -99,28 +84,15 @@ def voxel_grid(points, cell, device="cuda") -> VoxelGrid:
 
 
 def split_voxel(cfg) -> float:
-    c = cfg.get("split_voxel")
-    if c is None:
-        raise ValueError("split_voxel is not set in the config (metres, > 0)")
-    if isinstance(c, bool) or not isinstance(c, (int, float)) or not (float(c) > 0.0 and np.isfinite(float(c))):
-        raise ValueError(f"split_voxel must be a finite number of metres > 0, got {c!r}")
-    return float(c)
+    return instances3d.config_metres(cfg, "split_voxel")
 
 
 def split_min_points(cfg) -> int:
-    m = cfg.get("split_min_points", 1)
-    m = 1 if m is None else m
-    if isinstance(m, bool) or not isinstance(m, (int, float)) or m != m or int(m) != m or int(m) < 1:
-        raise ValueError(f"split_min_points must be an integer >= 1, got {m!r}")
-    return int(m)
+    return instances3d.positive_int("split_min_points", cfg.get("split_min_points"), 1)
 
 
 def split_mode(cfg) -> str:
-    m = cfg.get("split_mode", "split")
-    m = "split" if m is None else m
-    if m not in MODES:
-        raise ValueError(f"split_mode must be one of {MODES}, got {m!r}")
-    return m
+    return instances3d.one_of("split_mode", cfg.get("split_mode"), MODES, "split")
 
 
 def voxel_grid_for(geom_or_scene, cfg, device="cuda") -> VoxelGrid:
@@ -145,24 +117,10 @@ def split_rows(grid: VoxelGrid, rows, n_points, min_points=1, mode="split"):
     stay there).  mode "split": every component with >= min_points points, by (parent, points descending, anchor);
     "largest": per parent only the first of those.  Two read-backs: the element counts of the rows, then the kept
     components (past KEPT_FIRST_READ of them a third fetches the rest)."""
-    if not torch.is_tensor(rows) or not rows.is_cuda:
-        raise ValueError("split_rows takes device bit rows (no CPU path)")
-    if rows.dtype != i64 or rows.dim() != 2:
-        raise TypeError("split_rows: int64 [K][nw] bit rows expected")
-    if mode not in MODES:
-        raise ValueError(f"split_rows: mode must be one of {MODES}, got {mode!r}")
-    if isinstance(min_points, bool) or int(min_points) != min_points or int(min_points) < 1:
-        raise ValueError(f"split_rows: min_points must be an integer >= 1, got {min_points!r}")
-    n, min_points = int(n_points), int(min_points)
-    if n != grid.n_points:
-        raise ValueError(f"split_rows: rows over {n} points, the grid holds {grid.n_points}")
-    rows = rows.contiguous()
-    k, nw, v, dev = int(rows.shape[0]), int(rows.shape[1]), grid.n_voxels, rows.device
-    if nw < (n + 63) // 64:
-        raise ValueError(f"split_rows: rows of {nw} words for {n} points")
-    if grid.vox.device != dev:
-        raise ValueError("split_rows: the rows and the grid live on different devices")
-    none = lambda: (torch.zeros((0, nw), dtype=i64, device=dev), torch.zeros(0, dtype=i64), torch.zeros(0, dtype=i64))
+    rows, k, nw, n, dev = instances3d.check_rows("split_rows", rows, n_points, grid.n_points, "grid", grid.vox)
+    instances3d.one_of("split_rows: mode", mode, MODES)
+    min_points, v = instances3d.positive_int("split_rows: min_points", min_points), grid.n_voxels
+    none = lambda: instances3d.no_rows(nw, dev)
     if k == 0 or n == 0 or v == 0:
         return none()
     vw = (v + 63) // 64
@@ -180,38 +138,7 @@ def split_rows(grid: VoxelGrid, rows, n_points, min_points=1, mode="split"):
             return none()
         parent = torch.empty(t, dtype=i32, device=dev)
         call("bff_split_union", _ptr(occ), _ptr(prefix), _ptr(elem_offs), k, v, _ptr(grid.nbr, i32), t, _ptr(parent))
-        count = torch.empty(t, dtype=i32, device=dev)
-        kept = torch.empty((1 + t, 2), dtype=i32, device=dev)
-        call("bff_split_count", *head, _ptr(elem_offs), _ptr(parent), t, min_points, _ptr(count), _ptr(kept))
-        first = min(t, KEPT_FIRST_READ)
-        got = kept[:1 + first].cpu().numpy()                                  # read-back 2: the kept components
-        n_kept = int(got[0, 0])
-        if n_kept > first:
-            got = np.concatenate([got, kept[1 + first:1 + n_kept].cpu().numpy()])
-        elem, pts = got[1:1 + n_kept, 0].astype(np.int64), got[1:1 + n_kept, 1].astype(np.int64)
-        par = np.searchsorted(offs, elem, side="right") - 1
-        order = np.lexsort((elem, -pts, par))                                  # within a row, element order = anchor order
-        if mode == "largest" and len(order):
-            p = par[order]
-            order = order[np.concatenate([[True], p[1:] != p[:-1]])]
-        r = len(order)
-        if r == 0:
-            return none()
-        table = torch.full((t,), -1, dtype=i32, device=dev)
-        table[torch.from_numpy(elem[order]).to(dev)] = torch.arange(r, dtype=i32, device=dev)
-        out = torch.empty((r, nw), dtype=i64, device=dev)
-        call("bff_split_emit", *head, _ptr(elem_offs), _ptr(parent), t, _ptr(table), r, _ptr(out))
-    return out, torch.from_numpy(par[order].astype(np.int64)), torch.from_numpy(pts[order])
-
-
-def _take(conf, parent):
-    """conf[parent] in conf's own container kind and dtype."""
-    idx = parent.tolist()
-    if isinstance(conf, (list, tuple)):
-        return type(conf)(conf[i] for i in idx)
-    if torch.is_tensor(conf):
-        return conf.reshape(-1)[parent.to(conf.device)]
-    return np.asarray(conf).reshape(-1)[np.asarray(idx, dtype=np.int64)]
+        return instances3d.emit_kept(head, elem_offs, offs, parent, t, min_points, mode, nw) or none()
 
 
 def split_instances(grid: VoxelGrid, result, cfg):
@@ -219,19 +146,8 @@ def split_instances(grid: VoxelGrid, result, cfg):
     original point order, `conf`, `final_class`).  -> the same kind with `rows` replaced by the parts and `conf`,
     `final_class` taken from each part's parent, plus the attribute `parent` (int64 [R], host).  A result whose rows is
     None comes back as it is.  Config keys: split_min_points, split_mode (split_voxel made the grid)."""
-    import copy
     rows = getattr(result, "rows", None)
     if rows is None:
         return result
     out_rows, parent, _ = split_rows(grid, rows, grid.n_points, split_min_points(cfg), split_mode(cfg))
-    classes = list(result.final_class)
-    new = copy.copy(result)
-    new.rows = out_rows
-    new.final_class = [classes[i] for i in parent.tolist()]
-    new.conf = _take(result.conf, parent)
-    if getattr(result, "conf_host", None) is not None:
-        new.conf_host = _take(result.conf_host, parent)
-    if getattr(result, "prefetch", None) is not None:                       # a Stage2Result's refinement inputs: of the
-        new.prefetch = None                                                 # unsplit rows
-    new.parent = parent
-    return new
+    return instances3d.replace_rows(result, out_rows, parent)

@@ -21,7 +21,7 @@ import dataclasses
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, instances3d
 from ._lib import _ptr, call, i32, i64
 
 MODES = ("snap", "exclusive")
@@ -117,34 +117,17 @@ def superpoints_from_grid(grid) -> SuperpointIndex:
     return superpoint_index(grid.vox)
 
 
-def _positive_int(name, m, default=1):
-    m = default if m is None else m
-    if isinstance(m, bool) or not isinstance(m, (int, float)) or m != m or int(m) != m or int(m) < 1:
-        raise ValueError(f"{name} must be an integer >= 1, got {m!r}")
-    return int(m)
-
-
-def _ratio(name, r):
-    if isinstance(r, bool) or not isinstance(r, (int, float)) or not (0.0 < float(r) <= 1.0):      # NaN fails both
-        raise ValueError(f"{name} must be a number in (0, 1], got {r!r}")
-    return float(r)
-
-
 def snap_ratio(cfg) -> float:
-    r = cfg.get("snap_ratio", 0.5)
-    return _ratio("snap_ratio", 0.5 if r is None else r)
+    r = cfg.get("snap_ratio")
+    return instances3d.ratio("snap_ratio", 0.5 if r is None else r)
 
 
 def snap_mode(cfg) -> str:
-    m = cfg.get("snap_mode", "snap")
-    m = "snap" if m is None else m
-    if isinstance(m, bool) or m not in MODES:
-        raise ValueError(f"snap_mode must be one of {MODES}, got {m!r}")
-    return m
+    return instances3d.one_of("snap_mode", cfg.get("snap_mode"), MODES, "snap")
 
 
 def snap_min_points(cfg) -> int:
-    return _positive_int("snap_min_points", cfg.get("snap_min_points", 1))
+    return instances3d.positive_int("snap_min_points", cfg.get("snap_min_points"), 1)
 
 
 def snap_rows(index: SuperpointIndex, rows, n_points, ratio=0.5, mode="snap", min_points=1):
@@ -152,23 +135,11 @@ def snap_rows(index: SuperpointIndex, rows, n_points, ratio=0.5, mode="snap", mi
     and zero in the result.  -> (rows_out int64 [R][nw] on the device, parent int64 [R], points int64 [R]; the two lists
     are decided on the host and stay there): the rows that keep at least min_points points, in their order.  One
     read-back: the point counts."""
-    if not torch.is_tensor(rows) or not rows.is_cuda:
-        raise ValueError("snap_rows takes device bit rows (no CPU path)")
-    if rows.dtype != i64 or rows.dim() != 2:
-        raise TypeError("snap_rows: int64 [K][nw] bit rows expected")
-    if isinstance(mode, bool) or mode not in MODES:
-        raise ValueError(f"snap_rows: mode must be one of {MODES}, got {mode!r}")
-    ratio, min_points = _ratio("snap_rows: ratio", ratio), _positive_int("snap_rows: min_points", min_points)
-    n = int(n_points)
-    if n != index.n_points:
-        raise ValueError(f"snap_rows: rows over {n} points, the index holds {index.n_points}")
-    rows = rows.contiguous()
-    k, nw, s, dev = int(rows.shape[0]), int(rows.shape[1]), index.n_segments, rows.device
-    if nw < (n + 63) // 64:
-        raise ValueError(f"snap_rows: rows of {nw} words for {n} points")
-    if index.seg.device != dev:
-        raise ValueError("snap_rows: the rows and the index live on different devices")
-    none = lambda: (torch.zeros((0, nw), dtype=i64, device=dev), torch.zeros(0, dtype=i64), torch.zeros(0, dtype=i64))
+    rows, k, nw, n, dev = instances3d.check_rows("snap_rows", rows, n_points, index.n_points, "index", index.seg)
+    instances3d.one_of("snap_rows: mode", mode, MODES)
+    ratio = instances3d.ratio("snap_rows: ratio", ratio)
+    min_points, s = instances3d.positive_int("snap_rows: min_points", min_points), index.n_segments
+    none = lambda: instances3d.no_rows(nw, dev)
     if k == 0 or n == 0:
         return none()
     with torch.cuda.device(dev):
@@ -201,21 +172,8 @@ def snap_instances(index: SuperpointIndex, result, cfg):
     original point order, `conf`, `final_class`).  -> the same kind with `rows` replaced by the snapped rows that survive
     and `conf`, `final_class` taken from each one's parent, plus the attribute `parent` (int64 [R], host).  A result whose
     rows is None comes back as it is.  Config keys: snap_ratio, snap_mode, snap_min_points."""
-    import copy
-
-    from .spatial import _take
     rows = getattr(result, "rows", None)
     if rows is None:
         return result
     out_rows, parent, _ = snap_rows(index, rows, index.n_points, snap_ratio(cfg), snap_mode(cfg), snap_min_points(cfg))
-    classes = list(result.final_class)
-    new = copy.copy(result)
-    new.rows = out_rows
-    new.final_class = [classes[i] for i in parent.tolist()]
-    new.conf = _take(result.conf, parent)
-    if getattr(result, "conf_host", None) is not None:
-        new.conf_host = _take(result.conf_host, parent)
-    if getattr(result, "prefetch", None) is not None:                       # a Stage2Result's refinement inputs: of the
-        new.prefetch = None                                                 # rows before the snap
-    new.parent = parent
-    return new
+    return instances3d.replace_rows(result, out_rows, parent)

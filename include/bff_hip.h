@@ -1157,7 +1157,8 @@ int bff_lift_bits(const uint64_t *cols, int64_t n_source, int32_t n_rows, const 
  *   bff_dbscan_core      the density pass: core u64 [K][ceil(N / 64)]
  *   bff_dbscan_link      unions over the core elements (compare-and-swap, the larger root under the smaller), a flatten
  *                        that only reads, then every non-core element's slot written by its own thread: parent[e] = the
- *                        smallest core element of e's cluster, -1 for noise
+ *                        smallest core element of e's cluster, -1 for noise.  The forest's kernels are
+ *                        bff_split_union's and the walk over a point's 27 cells is bff_nn_search's (csrc/cells.h)
  *   bff_split_count, bff_split_emit   unchanged, called with vox[p] = p (-1 for a non-finite point), n_voxels = N, rows =
  *                        occ = set: they accept any point-to-cell map, a parent of -1 is followed nowhere, and a root
  *                        is an element with parent[e] == e.  Within a row, element order is point order, so the root of a

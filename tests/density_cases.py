@@ -54,6 +54,20 @@ def duplicates(n=200):
     return np.concatenate([np.full((n, 3), 0.5), [[0.625, 0.5, 0.5]], [[3.0, 3.0, 3.0]]])
 
 
+def five_groups():
+    """70 points (two words a row) in six groups of (14, 10, 12, 12, 12, 10) points: a group sits within eps / 2 of its
+    centre and the centres are 4 apart, so at eps or at a cell of EPS a group is one part and no two groups touch.  The
+    point order is shuffled: every group has points in both words.  Row 0 holds the first five groups -- five kept parts,
+    three of them tied in points -- and row 1 the sixth.  -> (points, rows int64 [2][2])."""
+    rng = np.random.default_rng(9)
+    sizes = (14, 10, 12, 12, 12, 10)
+    group = np.repeat(np.arange(6), sizes)
+    pts = np.array([[4.0 * g, 0.0, 0.0] for g in group]) + rng.integers(0, 8, (70, 3)) / 64.0
+    perm = rng.permutation(70)
+    pts, group = pts[perm], group[perm]
+    return pts, pack(np.stack([group < 5, group == 5]))
+
+
 def garbage(rows, n):
     """The rows with a spare word, every bit at a position >= n set."""
     rows = np.concatenate([rows, np.zeros((rows.shape[0], 1), np.int64)], axis=1)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import density_cases as dc
 import spatial_ref as sr
 import test_spatial_host as th
 
@@ -216,6 +217,21 @@ def test_selection(sp):
         sp.split_rows(grid, dev_rows(rows), n, 1, "dbscan")
     with pytest.raises(ValueError, match="min_points"):
         sp.split_rows(grid, dev_rows(rows), n, 0)
+
+
+@pytest.mark.parametrize("mode", ["split", "largest"])
+def test_more_kept_parts_than_the_first_read_fetches(sp, monkeypatch, mode):
+    """Six kept parts, five of them in row 0, against a first read of two: the rest comes with the overflow fetch, and the
+    result is the statement's and the one of a first read that holds them all."""
+    from beyond_fixed_forms_amd import instances3d
+    pts, rows = dc.five_groups()
+    grid = sp.voxel_grid(pts, dc.EPS, DEV)
+    whole = [t.cpu() for t in sp.split_rows(grid, dev_rows(rows), 70, 1, mode)]
+    monkeypatch.setattr(instances3d, "KEPT_FIRST_READ", 2)
+    exp = check_split(sp, pts, dc.EPS, rows, 1, mode, grid=grid)
+    assert exp[2].tolist() == ([14, 12, 12, 12, 10, 10] if mode == "split" else [14, 10]) and exp[1].tolist()[-1] == 1
+    again = [t.cpu() for t in sp.split_rows(grid, dev_rows(rows), 70, 1, mode)]
+    assert all(torch.equal(a, b) for a, b in zip(whole, again))
 
 
 # ------------------------------------------------------------------ the random case
