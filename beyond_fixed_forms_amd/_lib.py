@@ -27,6 +27,8 @@ SIGNATURES = {
     "bff_project_views_lookup": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _D, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P],
     "bff_project_views_cached": [_L, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P],
     "bff_visibility_table": [_P, _L, _L, _P, _P, _I, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _L, _P, _I, _P],
+    "bff_visibility_sorted": [_P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "bff_project_views_runs": [_L, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P],
     "bff_masks2d_count": [_P, _I, _L, _P, _P, _P],
     "bff_masks2d_runs": [_P, _I, _L, _P, _P, _P, _P],
     "bff_project_views": [_P, _L, _L, _P, _P, _I, _P, _P, _I, _I, _D, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P],
@@ -116,6 +118,8 @@ PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, [
          "bff_host_component_csr": (c_int32, [_P, _P, _I, _I, _P, _P, _P, _P]),
          "bff_visibility_words": (c_int64, [c_int64]), "bff_visibility_builds": (c_int64, []),
          "bff_visibility_table_bytes": (c_int32, [c_int64, c_int32, c_int64, _P]),
+         "bff_visibility_sorted_bytes": (c_int32, [c_int32, c_int32, c_int64, _P]),
+         "bff_sweep_runs_ok": (c_int32, [c_int64]),
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
@@ -402,11 +406,12 @@ def visibility_table_bytes(n_points, n_slots, n_pixels=0):
 
 
 def visibility_table(xyz_soa, n_points, slot_inv_pose, cam_intr, depth, height, width, depth_thresh, tile_bounds=None,
-                     depth_size=None, max_bytes=None):
+                     depth_size=None, max_bytes=None, with_count=False):
     """The visibility table of a resident scene (bff_visibility_table), built on the current stream: (vis_mask int64
     [n_slots][visibility_words], vis_off int32 [n_slots][visibility_words], vis_pix int32 [n_pixels]) for the depth slots
     `depth` holds, slot s seen with slot_inv_pose[s] (f64 [n_slots][16]).  Waits once, for the number of visible pairs
-    between the offsets and the pixel pass.  max_bytes: None is returned instead of a table larger than that."""
+    between the offsets and the pixel pass.  max_bytes: None is returned instead of a table larger than that.  with_count:
+    the number of visible pairs comes fourth (vis_pix keeps one element when there is none)."""
     dev = xyz_soa.device
     n_slots = int(slot_inv_pose.shape[0])
     stride = visibility_words(n_points)
@@ -424,7 +429,7 @@ def visibility_table(xyz_soa, n_points, slot_inv_pose, cam_intr, depth, height, 
         return None
     pix = torch.empty(max(n_pixels, 1), dtype=i32, device=dev)
     call("bff_visibility_table", *head, _ptr(pix, i32), n_pixels, _ptr(total, i64), 2)
-    return mask, off, pix
+    return (mask, off, pix, n_pixels) if with_count else (mask, off, pix)
 
 
 def project_views_cached(n_points, depth_index, height, width, vis, mask_tab, mask_dir, run_start, run_end, view_mask_offs,
@@ -436,6 +441,60 @@ def project_views_cached(n_points, depth_index, height, width, vis, mask_tab, ma
          _ptr(vis[0], i64), _ptr(vis[1], i32), _ptr(vis[2], i32), _ptr(mask_tab, i32), _ptr(mask_dir, i32),
          _ptr(run_start, i32), _ptr(run_end, i32), _ptr(view_mask_offs, i32), word_bits, _ptr(frame_mask, i32),
          _ptr(frame_rowbase, i32), _ptr(frame_nmask, i32), _ptr(frame_flags, i32), _ptr(rows, i64),
+         0 if rows is None else rows.shape[0], (n_points + 63) // 64, _ptr(chunk_mask, i64), _ptr(masked_count, i32),
+         _ptr(viewed_count, i32))
+
+
+def visibility_sorted_bytes(n_slots, height, n_pixels=0):
+    """(bytes of vis_spix, of vis_spt, of vis_rowstart): what the pixel-sorted companion adds to a table
+    (bff_visibility_sorted_bytes)."""
+    out = (c_int64 * 3)()
+    rc = load().bff_visibility_sorted_bytes(n_slots, height, n_pixels, ctypes.cast(out, c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"bff_visibility_sorted_bytes failed ({rc}): {load().bff_last_error().decode()}")
+    return tuple(int(v) for v in out)
+
+
+sorted_temp_bytes = 0          # scratch of the last visibility_sorted call (temporary: keys, points, sorted keys, the sort's own)
+
+
+def visibility_sorted(vis, n_pixels, n_points, height, width):
+    """The pixel-sorted companion (vis_spix int32 [n_pixels], vis_spt int32 [n_pixels], vis_rowstart int32
+    [n_slots][height + 1]) of the table `vis` = (vis_mask, vis_off, vis_pix) of visibility_table with n_pixels visible
+    pairs, built on the current stream (bff_visibility_sorted).  Like vis_pix the two lists keep one element when there is
+    no pair.  Nothing waits; the scratch goes back to the allocator, stream-ordered."""
+    global sorted_temp_bytes
+    mask, off, pix = vis
+    dev = mask.device
+    n_slots = int(mask.shape[0])
+    spix = torch.empty(max(n_pixels, 1), dtype=i32, device=dev)
+    spt = torch.empty(max(n_pixels, 1), dtype=i32, device=dev)
+    rowstart = torch.zeros((n_slots, height + 1), dtype=i32, device=dev)
+    need = ctypes.c_size_t(0)
+    args = (n_pixels, n_points, n_slots, height, width)
+    call("bff_visibility_sorted", None, None, None, *args, None, None, None, None, ctypes.byref(need))
+    sorted_temp_bytes = int(need.value)
+    temp = torch.empty(max(int(need.value), 1), dtype=u8, device=dev)
+    call("bff_visibility_sorted", _ptr(mask, i64), _ptr(off, i32), _ptr(pix, i32), *args, _ptr(spix, i32), _ptr(spt, i32),
+         _ptr(rowstart, i32), _ptr(temp), ctypes.byref(need))
+    return spix, spt, rowstart
+
+
+def sweep_runs_ok(n_points):
+    """Does the cached sweep of a scene with n_points take the run-major form (bff_sweep_runs_ok: the LDS bound,
+    BFF_SWEEP_RUNS, BFF_SWEEP_RUNS_LDS_BYTES; read per call)?"""
+    return bool(load().bff_sweep_runs_ok(n_points))
+
+
+def project_views_runs(n_points, depth_index, height, width, vis, vis_sorted, run_start, run_end, mask_run_offs,
+                       view_mask_offs, word_bits, frame_mask, frame_rowbase, frame_nmask, frame_flags, rows, masked_count,
+                       viewed_count, chunk_mask):
+    """project_views_cached asked from the masks' side: `vis_sorted` = (vis_spix, vis_spt, vis_rowstart) of
+    visibility_sorted, no row directory (bff_project_views_runs)."""
+    call("bff_project_views_runs", n_points, depth_index.shape[0], _ptr(depth_index, i32), height, width,
+         _ptr(vis[0], i64), _ptr(vis_sorted[0], i32), _ptr(vis_sorted[1], i32), _ptr(vis_sorted[2], i32),
+         _ptr(run_start, i32), _ptr(run_end, i32), _ptr(mask_run_offs, i32), _ptr(view_mask_offs, i32), word_bits,
+         _ptr(frame_mask, i32), _ptr(frame_rowbase, i32), _ptr(frame_nmask, i32), _ptr(frame_flags, i32), _ptr(rows, i64),
          0 if rows is None else rows.shape[0], (n_points + 63) // 64, _ptr(chunk_mask, i64), _ptr(masked_count, i32),
          _ptr(viewed_count, i32))
 

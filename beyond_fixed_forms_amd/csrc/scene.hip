@@ -106,12 +106,15 @@ extern "C" int bff_scene_project_viewed(const bff_scene *sc, const bff_scene_par
         BFF_REQUIRE(ws->events[0] && ws->events[1] && ws->events[2] && ws->events[3], "bff_scene_project: a heavy stream needs the workspace's four events");
         BFF_TRY(hand_over(ws->events[0], stream, hv));
     }
-    // a1: 2-D RLE -> the masks' row directory, or the label plane (+ words where masks overlap, + segment bitmap)
-    if (lookup) {
+    // a1: 2-D RLE -> the masks' row directory, or the label plane (+ words where masks overlap, + segment bitmap); the
+    // run-major cached sweep walks the run tables themselves: nothing to build
+    const bool cached = lookup && sc->vis_mask && sc->vis_off && sc->vis_pix;
+    const bool runs = cached && sc->vis_spix && sc->vis_spt && sc->vis_rowstart && bff_sweep_runs_ok(n) != 0;
+    if (lookup && !runs) {
         BFF_REQUIRE(ws->mask_tab && ws->mask_dir, "bff_scene_project: no row directory buffers");
         BFF_TRY(bff_mask_row_directory(sc->run_start, sc->run_end, sc->mask_run_offs, n_rows, sc->height, sc->width,
                                        ws->mask_tab, ws->mask_dir, hv));
-    } else {
+    } else if (!lookup) {
         BFF_TRY(bff_rle_to_labels(sc->run_start, sc->run_end, sc->mask_run_offs, sc->view_mask_offs, sc->n_mviews, hw,
                                   sc->word_bits, ws->labels, ws->maskbits, ws->segmap, hv));
     }
@@ -121,7 +124,12 @@ extern "C" int bff_scene_project_viewed(const bff_scene *sc, const bff_scene_par
     // (bff_count_viewed over the scene's viewed frames, shared by the classes of the scene)
     int32_t *const sweep_viewed = (ratio && !viewed_in) ? ws->viewed : nullptr;
     const int32_t *const viewed = ratio ? (viewed_in ? viewed_in : ws->viewed) : nullptr;
-    if (lookup && sc->vis_mask && sc->vis_off && sc->vis_pix)      // the scene's visibility table answers geometry and depth
+    if (runs)                   // the table's pixel-sorted companion: every mask run finds the visible pairs it covers
+        BFF_TRY(bff_project_views_runs(n, sc->n_frames, sc->depth_index, sc->height, sc->width, sc->vis_mask, sc->vis_spix,
+                                       sc->vis_spt, sc->vis_rowstart, sc->run_start, sc->run_end, sc->mask_run_offs,
+                                       sc->view_mask_offs, sc->word_bits, sc->frame_mask, sc->frame_rowbase, sc->frame_nmask,
+                                       sc->frame_flags, ws->rows, n_rows, nw, ws->chunk_mask, ws->masked, sweep_viewed, hv));
+    else if (cached)            // the scene's visibility table answers geometry and depth
         BFF_TRY(bff_project_views_cached(n, sc->n_frames, sc->depth_index, sc->height, sc->width, sc->vis_mask, sc->vis_off,
                                          sc->vis_pix, ws->mask_tab, ws->mask_dir, sc->run_start, sc->run_end,
                                          sc->view_mask_offs, sc->word_bits, sc->frame_mask, sc->frame_rowbase, sc->frame_nmask,

@@ -40,7 +40,8 @@ class SceneStruct(ctypes.Structure):
                 ("height", c_int32), ("width", c_int32), ("n_frames", c_int32), ("n_mviews", c_int32),
                 ("word_bits", c_int32), ("n_rows", c_int32), ("conf_f16", c_int32), ("n_label_ids", c_int32),
                 ("s1_rows", c_int32), ("depth_h", c_int32), ("depth_w", c_int32), ("depth_tiled", c_int32),
-                ("vis_mask", c_void_p), ("vis_off", c_void_p), ("vis_pix", c_void_p)]
+                ("vis_mask", c_void_p), ("vis_off", c_void_p), ("vis_pix", c_void_p),
+                ("vis_spix", c_void_p), ("vis_spt", c_void_p), ("vis_rowstart", c_void_p)]
 
 
 class ParamsStruct(ctypes.Structure):
@@ -162,6 +163,7 @@ def scene_struct(ds, stage1=None, n_frames=None, vis=None):
         s.s1_rows = stage1.row_run_offs.shape[0] - 1
     if vis is not None:
         s.vis_mask, s.vis_off, s.vis_pix = _p(vis.mask), _p(vis.off), _p(vis.pix)
+        s.vis_spix, s.vis_spt, s.vis_rowstart = _p(vis.spix), _p(vis.spt), _p(vis.rowstart)
     return s
 
 

@@ -196,6 +196,13 @@ class VisibilityTable:
     pix: torch.Tensor             # int32 [visible pairs]
     ready: torch.cuda.Event       # recorded behind the build
     streams: set                  # raw handles of the streams that are already ordered behind the build
+    # the pixel-sorted companion (_lib.visibility_sorted) the run-major sweep walks, or None: the point-major sweep
+    spix: Optional[torch.Tensor] = None       # int32 [visible pairs]: flat pixel
+    spt: Optional[torch.Tensor] = None        # int32 [visible pairs]: point
+    rowstart: Optional[torch.Tensor] = None   # int32 [slots][height + 1]
+
+    def tensors(self):
+        return [t for t in (self.mask, self.off, self.pix, self.spix, self.spt, self.rowstart) if t is not None]
 
 
 def vis_table_max_bytes():
@@ -237,17 +244,26 @@ def scene_visibility(ds: DeviceScene, depth_thresh) -> Optional[VisibilityTable]
             first[slots] = idx
             poses = ds.inv_pose[torch.as_tensor(first).to(dev)].contiguous()
         got = _lib.visibility_table(ds.xyz, ds.n_points, poses, ds.cam_intr, ds.sweep_depth, ds.height, ds.width, key,
-                                    ds.tile_bounds, depth_size=ds.depth_size, max_bytes=vis_table_max_bytes())
+                                    ds.tile_bounds, depth_size=ds.depth_size, max_bytes=vis_table_max_bytes(), with_count=True)
         if got is None:
             tables[key] = False
             return None
+        # the companion counts against the same bound; a scene over it, over the 32-bit sort key or over the run-major
+        # sweep's LDS bound (or with BFF_SWEEP_RUNS=0) gets none and keeps the point-major form
+        got, n_pairs = got[:3], got[3]
+        n_slots = int(got[0].shape[0])
+        total = sum(_lib.visibility_table_bytes(ds.n_points, n_slots, n_pairs)) + \
+            sum(_lib.visibility_sorted_bytes(n_slots, ds.height, n_pairs))
+        companion = (None, None, None)
+        if _lib.sweep_runs_ok(ds.n_points) and total <= vis_table_max_bytes() and n_slots * ds.height * ds.width <= 1 << 32:
+            companion = _lib.visibility_sorted(got, n_pairs, ds.n_points, ds.height, ds.width)
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream(dev))
-        tab = tables[key] = VisibilityTable(*got, ready=ready, streams={raw})
+        tab = tables[key] = VisibilityTable(*got, ready, {raw}, *companion)
     elif raw not in tab.streams:
         st = torch.cuda.current_stream(ds.xyz.device)
         st.wait_event(tab.ready)
-        for t in (tab.mask, tab.off, tab.pix):
+        for t in tab.tensors():
             t.record_stream(st)
         tab.streams.add(raw)
     return tab
@@ -275,6 +291,8 @@ def projection_front(ds: DeviceScene, cfg, debug_out: bool = False, timers=None,
         fr = _Front(ds, cfg, {}, False, do_ratio=do_ratio, stage1=stage1)
         vis = scene_visibility(ds, DEPTH_THRESH)
         fr.dbg["sweep"] = "plain" if vis is None else "cached"
+        if vis is not None:     # what bff_scene_project decides for this call (the LDS bound and BFF_SWEEP_RUNS, read per call)
+            fr.dbg["sweep_form"] = "runs" if vis.spix is not None and _lib.sweep_runs_ok(ds.n_points) else "points"
         with sweep_span(timers, "project_views"), merge_span(timers, "merge_components"):
             fr.fast = pipeline.issue(ds, cfg, DEPTH_THRESH, stage1,
                                      ds.n_frames if (do_ratio and viewed_in is None) else ds.n_mask_frames, viewed_in, vis)

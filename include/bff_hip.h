@@ -824,6 +824,39 @@ int bff_project_views_cached(int64_t n_points, int32_t n_frames, const int32_t *
                              const int32_t *frame_flags, uint64_t *rows, int64_t n_rows, int64_t nw, uint64_t *chunk_mask,
                              int32_t *masked_count, int32_t *viewed_count, void *stream);
 
+/* Pixel-sorted companion of the visibility table: the visible pairs of every slot ordered by (flat pixel, point), so that a
+ * run [start, end) of a 2-D mask covers one contiguous range of its frame's slot.
+ *   vis_spix     uint32 [n_pixels]           flat pixel v * width + u
+ *   vis_spt      uint32 [n_pixels]           point index
+ *   vis_rowstart uint32 [n_slots][height+1]  absolute position of the slot's first pair with pixel >= y * width; entry
+ *                                            `height` is the slot's end (an empty slot: all equal)
+ * A pure function of the table: a stable radix sort of the pairs, which arrive in (slot, point) order, on the 32-bit key
+ * slot * height * width + pixel (n_slots * height * width <= 2^32), then one lower bound per (slot, image row).  No global
+ * atomics.  temp == NULL: only *temp_bytes is written (size query, no launch); the scratch (12 bytes per pair + the
+ * sort's own) is free again once the work on `stream` has run.  n_points == 0 or n_slots == 0: nothing is written. */
+int bff_visibility_sorted(const uint64_t *vis_mask, const uint32_t *vis_off, const uint32_t *vis_pix, int64_t n_pixels,
+                          int64_t n_points, int32_t n_slots, int32_t height, int32_t width, uint32_t *vis_spix,
+                          uint32_t *vis_spt, uint32_t *vis_rowstart, void *temp, size_t *temp_bytes, void *stream);
+/* bytes[3] = sizes of vis_spix, vis_spt and vis_rowstart: the persistent bytes the companion adds to the table's */
+int bff_visibility_sorted_bytes(int32_t n_slots, int32_t height, int64_t n_pixels, int64_t *bytes);
+
+/* bff_project_views_cached asked from the masks' side (same outputs, bit for bit, and profiling events): one workgroup per
+ * instance row = mask m of frame f walks the mask's runs over the slot's pixel-sorted pairs and ORs the covered points into
+ * a bitmap of the row in LDS, then stores its non-zero 32-byte sectors and the row's chunk flags (plain stores: `rows` is
+ * all zero on entry and a row belongs to one (frame, mask)); masked_count += the rows' column sums over the flagged chunks;
+ * viewed_count (may be NULL) += the table's bits of the frames with flag bit 0.  No row directory.  chunk_mask is required.
+ * The row must fit the LDS bound: bff_sweep_runs_ok(n_points) != 0 (64 KB: n_points <= 524 288; BFF_SWEEP_RUNS=0 answers 0
+ * for every scene and BFF_SWEEP_RUNS_LDS_BYTES lowers the bound, both read per call) -- bff_scene_project asks it and
+ * keeps bff_project_views_cached otherwise. */
+int32_t bff_sweep_runs_ok(int64_t n_points);
+int bff_project_views_runs(int64_t n_points, int32_t n_frames, const int32_t *depth_index, int32_t height, int32_t width,
+                           const uint64_t *vis_mask, const uint32_t *vis_spix, const uint32_t *vis_spt,
+                           const uint32_t *vis_rowstart, const int32_t *run_start, const int32_t *run_end,
+                           const int32_t *mask_run_offs, const int32_t *view_mask_offs, int32_t word_bits,
+                           const int32_t *frame_mask, const int32_t *frame_rowbase, const int32_t *frame_nmask,
+                           const int32_t *frame_flags, uint64_t *rows, int64_t n_rows, int64_t nw, uint64_t *chunk_mask,
+                           int32_t *masked_count, int32_t *viewed_count, void *stream);
+
 /* Device-resident inputs of one scene (what scene.prepare_scene uploads; all pointers are device pointers). */
 typedef struct bff_scene {
     int64_t n_points, n_pad, nw;
@@ -844,6 +877,9 @@ typedef struct bff_scene {
             depth_tiled;            /* depth_layout of bff_project_views_u16: 0 uint16 rows, 1 uint16 tiles, 2 float32 tiles */
     const uint64_t *vis_mask;       /* the scene's visibility table (bff_visibility_table, built for params.depth_thresh) or */
     const uint32_t *vis_off, *vis_pix;     /* NULL: with all three set and masks looked up, the sweep is bff_project_views_cached */
+    const uint32_t *vis_spix, *vis_spt, *vis_rowstart;    /* the table's pixel-sorted companion (bff_visibility_sorted) or NULL:
+                                       with these set too and bff_sweep_runs_ok(n_points), the sweep is bff_project_views_runs
+                                       and no row directory is built */
 } bff_scene;
 
 typedef struct bff_scene_params {
