@@ -1,6 +1,6 @@
 // Per-point camera geometry as device functions: the arithmetic contract of bff_project_views (include/bff_hip.h) and the
-// exact frustum test of a point tile, stated once for kernels that are not the sweep itself (render_depth.hip).  The
-// sweep kernels of project.hip spell the same expressions out in their frame loops; tests hold both to the same checker.
+// exact frustum test of a point tile, stated once for the sweep kernels (project.hip, visibility.hip, diag.hip) and the
+// renderers (render_depth.hip, render_labels.hip).
 #pragma once
 
 #include "common.h"
@@ -8,6 +8,13 @@
 namespace bff {
 
 struct CameraK { double k[9]; };          // row-major intrinsics, passed as a kernel argument
+
+inline CameraK camera_k(const double *cam_intr_host)    // from the caller's nine doubles; null: zeros (no geometry is run)
+{
+    CameraK K{};
+    for (int i = 0; i < 9 && cam_intr_host; ++i) K.k[i] = cam_intr_host[i];
+    return K;
+}
 
 // World point -> camera z and rounded pixel.  c_i: k-ascending fma chain of inv_pose row i with (x, y, z, 1) from +0.0;
 // p_i: fma chain of K row i with c; u = rint(p_0 / c_2), v = rint(p_1 / c_2) (IEEE division, half to even).  P: the
@@ -30,10 +37,17 @@ __host__ __device__ __forceinline__ bool pixel_in_bounds(double u, double v, dou
     return (u >= 0.0) && (u < dW) && (v >= 0.0) && (v < dH);
 }
 
-// Frustum culling of one wave's point tile against the <= 8 frames [g0, g1): lane = 8 * frame + corner of the tile's box
-// bb = (xmin, ymin, zmin, xmax, ymax, zmax).  Bit 8 k of the result: frame g0 + k cannot hold an in-bounds pixel of any
-// point inside the box (the half-space test documented at project_views_kernel: both cones, margins 0.01 pixel and 1e-6,
-// NaN / inf corners keep the frame).  Must be called by all 64 lanes.
+// Frustum culling of one wave's point tile against the <= 8 frames [g0, g1), all at once: lane = 8 * frame + corner of the
+// tile's box bb = (xmin, ymin, zmin, xmax, ymax, zmax).  Bit 8 k of the result: frame g0 + k cannot hold an in-bounds pixel
+// of any point inside the box.  A point can only be visible if its pixel is in bounds, i.e. (exact arithmetic) it lies in
+// the double cone  {L_i >= 0 for all i, c_z > 0}  u  {L_i <= 0 for all i, c_z < 0}  with
+//   L_1 = p_0 + (1/2 + m) c_z,  L_2 = (W - 1/2 + m) c_z - p_0,  L_3 = p_1 + (1/2 + m) c_z,  L_4 = (H - 1/2 + m) c_z - p_1
+// (the two image borders in u and in v, widened by m = 0.01 pixel; the reference has no z > 0 test, hence both cones).
+// Each L_i is an affine function of the world point, so its value anywhere in the box is a convex combination of the 8
+// corner values: if some L_i < -delta at every corner the box misses the front cone, if some L_j > +delta at every corner
+// it misses the back cone; a frame is skipped only when both hold.  delta = 1e-6 and m exceed the float64 rounding of these
+// forms (~1e-11) by orders of magnitude; NaN / inf corner values compare false and keep the frame.  Exact: a skipped frame
+// has no in-bounds point in this wave.  Must be called by all 64 lanes.
 __device__ __forceinline__ uint64_t cull_frames(const double *__restrict__ bb, const double *__restrict__ inv_pose,
                                                 const CameraK &K, int g0, int g1, int lane, double dW, double dH)
 {

@@ -85,7 +85,7 @@ __device__ __forceinline__ void offer_box(const TexelBox &b, uint32_t key, int l
     }
 }
 
-// The point z-buffer.  viewed_count_kernel's shape (project.hip): 256 threads own 1024 consecutive points, 4 per thread in
+// The point z-buffer.  viewed_count_kernel's shape (visibility.hip): 256 threads own 1024 consecutive points, 4 per thread in
 // registers across the frames of the block's frame tile (blockIdx.y), poses wave-uniform, the tile culled against
 // tile_bounds in groups of 8 frames.  Per frame and point: the key to the point's own texel; kSplat: also to the texels
 // whose sample point lies within (Rx, Ry) pixels of the point's integer pixel, a rectangle found per axis (splat_range).
