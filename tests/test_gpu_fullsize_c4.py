@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import projection_ref as pref
+from test_gpu_sweep_runs import assert_same, snapshot
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(os.environ.get("BFF_SKIP_C4") == "1", reason="config 4 skipped on request")]
@@ -77,6 +78,41 @@ def test_c4_checksums_layout_and_sweeps(c4):
                        ds_plain.height, ds_plain.width, 0.08, None, 64, ds_plain.frame_mask, ds_plain.frame_rowbase,
                        ds_plain.frame_nmask, torch.ones_like(zero_flags), None, None, v_a)
     assert torch.equal(rows_a, raw) and torch.equal(m_a, masked) and torch.equal(v_a, viewed)
+
+
+def test_c4_sweeps_cached_with_the_same_result(c4, monkeypatch, capsys):
+    """Three projections of one fresh DeviceScene of the config-4 scene by the one-call path: plain, then twice from the
+    scene's visibility table.  A row of 10^6 points is over the run-major form's LDS bound, so the cached sweeps are the
+    point-major form at 1 000 000 points, 600 slots and 64-bit mask words; everything a caller receives equals the plain
+    projection.  The table's size is printed; BFF_VIS_TABLE_MAX_MB is raised for this test so that the form does not hang
+    on the default bound.  Measured on an MI355X: 55 276 811 visible pairs in 600 slots, 75.0 MB of bits + 37.5 MB of offsets
+    + 221.1 MB of pixels = 318.2 MiB, which also fits the default bound of 512 MB."""
+    from beyond_fixed_forms_amd import _lib
+    from beyond_fixed_forms_amd.projection import DEPTH_THRESH, projection_back, projection_front
+    from beyond_fixed_forms_amd.scene import prepare_scene
+    scene, cfg, _ = c4
+    monkeypatch.setenv("BFF_VIS_TABLE_MAX_MB", "4096")
+    assert not _lib.sweep_runs_ok(scene.points.shape[0])
+    ds = prepare_scene(scene, cfg, device=DEV)
+    kinds, snaps = [], []
+    for _ in range(3):
+        res = projection_back(projection_front(ds, cfg))
+        kinds.append((res.debug["sweep"], res.debug.get("sweep_form")))
+        snaps.append(snapshot(res))
+        del res
+    torch.cuda.synchronize()
+    tab = ds.__dict__.get("_vis_tables", {}).get(float(DEPTH_THRESH))
+    if tab not in (None, False, "visited"):
+        pairs, n_slots = int(tab.pix.shape[0]), int(tab.mask.shape[0])
+        size = _lib.visibility_table_bytes(ds.n_points, n_slots, pairs)
+        with capsys.disabled():
+            print(f"\nconfig-4 visibility table: {n_slots} slots, {pairs} pairs, bytes (mask, off, pix) = {size}, "
+                  f"{sum(size) / (1 << 20):.1f} MB in all")
+        assert tab.spix is None
+    assert kinds == [("plain", None), ("cached", "points"), ("cached", "points")], kinds
+    assert snaps[0]["path"].startswith("fast") and snaps[0]["rows"].shape[0] >= 1
+    assert_same(snaps[0], snaps[1])
+    assert_same(snaps[0], snaps[2])
 
 
 def test_c4_components_two_formulations_agree(c4):

@@ -145,22 +145,7 @@ def test_runs_sweep_equals_points_sweep(lib, tiles, wb, p):
 
 
 # ------------------------------------------------------------------ 3. hand-made masks against brute force
-HW = vr.H * vr.W
-DEPTH_INDEX = np.array([2, 0, 5, 3, 1, 4, 0], np.int32)          # another order than the slots; slot 0 twice
-FRAME_MASK = np.array([0, 0, 0, 0, 0, 0, -1], np.int32)          # the last frame is viewed only
-FRAME_FLAGS = np.array([1, 1, 0, 1, 3, 1, 1], np.int32)          # frame 2 has masks and does not count as viewed
-
-
-def hand_masks(free_pixel):
-    return [[(40, 100)],                                         # crosses two row ends
-            [(0, HW)],                                           # the whole image
-            [(0, 1), (HW - 1, HW)],                              # one pixel at each end
-            [(10, 20), (45, 50), (300, 420)],
-            [],                                                  # no runs, between two masks that have some
-            [(200, 260)],
-            [(free_pixel, free_pixel + 1)],                      # hits no visible point
-            [(500, 540), (600, 610)],
-            [(500, 540), (600, 610)]]                            # identical to the one before
+HW, DEPTH_INDEX, FRAME_MASK, FRAME_FLAGS, hand_masks = sr.HW, sr.DEPTH_INDEX, sr.FRAME_MASK, sr.FRAME_FLAGS, sr.hand_masks
 
 
 @pytest.mark.parametrize("n", [1500, 1100, 1])

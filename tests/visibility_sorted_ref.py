@@ -75,3 +75,23 @@ def membership_sweep(xyz, poses, k33, depths, thresh, depth_index, frame_mask, f
     flags[:, :n_chunks] = bits.reshape(bits.shape[0], n_chunks, 512).any(axis=2)
     cmask = np.packbits(flags, axis=1, bitorder="little").view(np.uint64)
     return np.ascontiguousarray(rows), cmask, bits[:, :n].sum(axis=0, dtype=np.int32), viewed
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The hand-made case over visibility_ref's 24 x 32 image: seven frames over its six slots and one view of nine masks.
+HW = vr.H * vr.W
+DEPTH_INDEX = np.array([2, 0, 5, 3, 1, 4, 0], np.int32)          # another order than the slots; slot 0 twice
+FRAME_MASK = np.array([0, 0, 0, 0, 0, 0, -1], np.int32)          # the last frame is viewed only
+FRAME_FLAGS = np.array([1, 1, 0, 1, 3, 1, 1], np.int32)          # frame 2 has masks and does not count as viewed
+
+
+def hand_masks(free_pixel):
+    return [[(40, 100)],                                         # crosses two row ends
+            [(0, HW)],                                           # the whole image
+            [(0, 1), (HW - 1, HW)],                              # one pixel at each end
+            [(10, 20), (45, 50), (300, 420)],
+            [],                                                  # no runs, between two masks that have some
+            [(200, 260)],
+            [(free_pixel, free_pixel + 1)],                      # hits no visible point
+            [(500, 540), (600, 610)],
+            [(500, 540), (600, 610)]]                            # identical to the one before
