@@ -106,6 +106,8 @@ SIGNATURES = {
     "bff_dbscan_elements": [_P, _I, _L, _L, _P, _P, _P, _P, _P],
     "bff_dbscan_core": [_P, _I, _L, _P, _L, _P, _P, _P, _P, _L, _L, _P, _D, _D, _I, _P, _P],
     "bff_dbscan_link": [_P, _P, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _L, _L, _P, _D, _D, _I, _P, _P],
+    "bff_nms_pairs": [_P, _P, _P, _P, _I, _I, _F, _P, _P],
+    "bff_nms_greedy": [_P, _I, _P, _P, _P, _P],
 }
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
          "bff_masks2d_tile_pixels": (c_int32, []), "bff_label_runs_tile_pixels": (c_int32, []), "bff_mask_lookup_rows": (c_int32, [c_int32, c_int32, c_int64]),

@@ -17,7 +17,8 @@ against the ground truth in one process: AP, AP50, AP25 and the recalls into the
 Beside the path: `reproject_main` renders a stage's instances back into the colour frames as 2-D masks, `split_main` cuts
 them into their spatially connected parts, `cluster_main` into their density clusters, `snap_main` snaps them to the
 scan's superpoints, `subsample_main` writes a voxel subsample of every cloud and `lift_main` carries the instances of a run
-on it back to the full cloud; each writes to a directory of its own.  The four that turn a stage's files into files of
+on it back to the full cloud, and `assemble_main` gathers a scene's instances of all classes into one prediction, duplicates
+removed by a 3-D mask NMS (`evaluation_main --assembled` scores it); each writes to a directory of its own.  The four that turn a stage's files into files of
 the same format (split, cluster, snap, lift) are one driver, `_stage_main`, with a per-scene function each.
 """
 from __future__ import annotations
@@ -590,6 +591,86 @@ def lift_main(argv=None):
     return _stage_main(_lift_parser(), argv, ("lift_output_dir", "lift_target_npy_dir"), lift.lift_max_dist, scene)
 
 
+def _assemble_parser():
+    p = argparse.ArgumentParser(description="Beyond-Fixed-Forms: a scene's prediction assembled from all of its query "
+                                            "classes, with 3-D mask NMS (MI355X)")
+    p.add_argument("--config", type=str, required=True, help="Config")
+    which = p.add_mutually_exclusive_group(required=True)
+    which.add_argument("--cls", type=str, action="append", help="A class (repeatable); their order is the class index")
+    which.add_argument("--all-classes", action="store_true", help="Every sub-directory of the stage's directory, sorted")
+    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
+                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
+    p.add_argument("--point-labels", action="store_true",
+                   help="Also save point_instance (0 = none, else 1 + row) and point_semantic (class position, -1 = none)")
+    return p
+
+
+def assembled_dict(assembled, rle=False, point_labels=False):
+    """What assemble_main saves for one scene: the stage's file format ("ins" dense bool rows or, with rle, RLE dicts; "conf";
+    "final_class") plus "classes", "source" (int64 [R][2]: class position and row of every instance in its class's file) and
+    "removed_by"; with point_labels also "point_instance" and "point_semantic".  A scene without any row: the reference's
+    empty form with the same added keys."""
+    from . import assemble
+    r = int(assembled.rows.shape[0])
+    if r == 0:
+        out = {"ins": [], "conf": [], "final_class": []}
+    else:
+        ins = _lib.rows_to_rle(assembled.rows, assembled.n_points) if rle else \
+            _lib.unpack_rows(assembled.rows, assembled.n_points).cpu()
+        out = {"ins": ins, "conf": assembled.conf, "final_class": list(assembled.final_class)}
+    out["classes"] = list(assembled.classes)
+    out["source"] = torch.stack([assembled.source_class, assembled.source_row], dim=1)
+    out["removed_by"] = assembled.removed_by
+    if point_labels:
+        instance, semantic = assemble.point_labels(assembled)
+        out["point_instance"], out["point_semantic"] = instance.cpu(), semantic.cpu()
+    return out
+
+
+def assemble_main(argv=None):
+    """python tools/assemble_scene_3d.py --config configs/config.yaml (--cls a --cls b ... | --all-classes)
+                                          [--stage final|mask_3d] [--point-labels]
+    Scenes = the union of the classes' <scene>.pth names; a class without the scene contributes nothing.  Every scene's
+    rows of all classes become one set of instances (assemble.assemble_scene: NMS by score, optionally exclusive, small
+    ones dropped) saved to assembled_output_dir/<scene>.pth in the stage's file format.  Only the cloud's length is read."""
+    from . import assemble
+    args = _assemble_parser().parse_args(argv)
+    cfg = load_config(args.config)
+    stage_dir = cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir
+    if not os.path.isdir(stage_dir):
+        print(f"no {args.stage} output: {stage_dir} is not a directory", file=sys.stderr)
+        return 1
+    if args.all_classes:
+        classes = sorted(c for c in os.listdir(stage_dir) if os.path.isdir(os.path.join(stage_dir, c)))
+    else:
+        classes = list(dict.fromkeys(args.cls))
+    missing = [c for c in classes if not os.path.isdir(os.path.join(stage_dir, c))]
+    if missing or not classes:
+        print(f"no {args.stage} output for {missing if missing else 'any class'} under {stage_dir}", file=sys.stderr)
+        return 1
+    out_dir = cfg.get("assembled_output_dir")
+    if not out_dir:
+        raise ValueError("assembled_output_dir is not set in the config")
+    assemble.check_config(cfg)                                   # a bad value stops the run before the first scene
+    lists = {c: {s for s in os.listdir(os.path.join(stage_dir, c)) if s.endswith(".pth")} for c in classes}
+    _lib.load()
+    _host_threads()
+    device = "cuda"
+    os.makedirs(out_dir, exist_ok=True)
+    for name in sorted(set().union(*lists.values())):
+        scene_id = name[:-4]
+        print("Working on", scene_id, ":", sum(name in lists[c] for c in classes), "classes")
+        n_points = int(_scene_cloud(cfg, scene_id, mmap_mode="r").shape[0])
+        # the stage's own output files, written by this project's scripts or the reference's (pickled dicts of tensors)
+        # (a class without the scene stands in as the empty form, so that class positions are those of the run's list)
+        results = {c: torch.load(os.path.join(stage_dir, c, name), map_location="cpu", weights_only=False)
+                   if name in lists[c] else {"ins": [], "conf": [], "final_class": []} for c in classes}
+        got = assemble.assemble_scene(results, n_points, cfg, device)
+        torch.save(assembled_dict(got, os.environ.get("BFF_SAVE_RLE") == "1", args.point_labels),
+                   os.path.join(out_dir, f"{scene_id}.pth"))
+    return 0
+
+
 def _evaluation_parser():
     """eval_scannet200.py:29-32 plus what the reference hard-codes (:74-76) or imports from its dataset tables."""
     p = argparse.ArgumentParser(description="Beyond-Fixed-Forms per-class evaluation (MI355X)")
@@ -602,13 +683,20 @@ def _evaluation_parser():
     p.add_argument("--label-table", type=str, required=True,
                    help='JSON {"class_labels": [...], "semantic_ids": [...]}: the evaluator\'s class names and the '
                         "dataset's raw semantic id of each")
+    p.add_argument("--assembled", action="store_true",
+                   help="Score the scenes' assembled predictions (assembled_output_dir/<scene>.pth, every class in one file) "
+                        "instead of final_output_dir/<cls>")
+    p.add_argument("--use-conf", action="store_true",
+                   help="Rank the predictions by the files' confidences instead of the reference's 1.0 for each")
     return p
 
 
 def evaluation_main(argv=None):
-    """python tools/eval_scannet200.py --cls "<class>" --label-table labels.json            (eval_scannet200.py:70-148)
-    The class's final files against the ground truth: AP, AP50, AP25 and the recalls of the class into its line of the
-    results file, every label's into result.txt beside it."""
+    """python tools/eval_scannet200.py --cls "<class>" --label-table labels.json [--assembled] [--use-conf]
+    (eval_scannet200.py:70-148)  The class's final files against the ground truth: AP, AP50, AP25 and the recalls of the
+    class into its line of the results file, every label's into result.txt beside it.  --assembled: the scenes' assembled
+    files (assemble_main), every class in one file, instead -- all scenes of assembled_output_dir are scored, so a class's
+    values equal its own run's where it has a file for each of them; --use-conf: the files' confidences instead of 1.0."""
     import json
 
     from . import evaluation as ev
@@ -620,9 +708,12 @@ def evaluation_main(argv=None):
     # `- 2 + 1` for scannet200 (EVAL:272-273) is what lines position p of it up with class_labels[p - 2]
     labels, semantic_ids = list(table["class_labels"]), list(table["semantic_ids"])
     cls = args.cls
-    data_path = os.path.join(cfg.final_output_dir, cls)
+    data_path = cfg.get("assembled_output_dir") if args.assembled else os.path.join(cfg.final_output_dir, cls)
+    if args.assembled and not data_path:
+        raise ValueError("assembled_output_dir is not set in the config")
     if not os.path.isdir(data_path):
-        print(f"no final output for class {cls!r}: {data_path} is not a directory", file=sys.stderr)
+        what = "assembled output" if args.assembled else f"final output for class {cls!r}"
+        print(f"no {what}: {data_path} is not a directory", file=sys.stderr)
         return 1
     _lib.load()
     _host_threads()
@@ -634,6 +725,13 @@ def evaluation_main(argv=None):
         truth = evaluator.prepare_ground_truth(sem_gt, np.asarray(loader[3]).astype(np.int32))
         result = torch.load(os.path.join(data_path, scene), map_location="cpu", weights_only=False)
         preds, rows = ev.final_file_predictions(result, scene.replace(".pth", ""), labels, truth.n_points, device)
+        if args.use_conf:
+            conf = result["conf"]
+            conf = conf.reshape(-1).tolist() if torch.is_tensor(conf) else list(conf)
+            if len(conf) != len(preds):
+                raise ValueError(f"{scene}: {len(preds)} instances and {len(conf)} confidences")
+            for pred, c in zip(preds, conf):
+                pred["conf"] = float(c)
         evaluator.add_scan(preds, ground_truth=truth, pred_rows=rows)
     avgs = evaluator.evaluate()
     results_dir = os.path.dirname(os.path.abspath(args.results_file))

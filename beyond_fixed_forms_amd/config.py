@@ -66,6 +66,15 @@ DEFAULTS = dict(
     # with fewer points is dropped; cluster_mode: "split" (every cluster becomes an instance) or "largest" (only the
     # largest cluster of each); cluster_output_dir: where the tool saves <cls>/<scene>.pth
     cluster_eps=None, cluster_min_samples=None, cluster_min_points=1, cluster_mode="split", cluster_output_dir=None,
+    # not keys of the reference either: a scene's prediction assembled from all of its query classes (assemble.py,
+    # tools/assemble_scene_3d.py).  assemble_nms_thres: in (0, 1], an instance that overlaps a better-scored one by at least
+    # this much is removed -- untuned, e.g. 0.5; absent or 0 = no NMS; assemble_criterion: "iou" or "containment" (the
+    # intersection over the smaller of the two); assemble_scope: "all" or "class" (only instances of one class remove each
+    # other); assemble_exclusive: every point goes to the best-scored instance that holds it; assemble_min_points: an
+    # instance with fewer points (after the exclusive step) is dropped; assembled_output_dir: where the tool saves
+    # <scene>.pth
+    assemble_nms_thres=None, assemble_criterion="iou", assemble_scope="all", assemble_exclusive=False,
+    assemble_min_points=1, assembled_output_dir=None,
 )
 
 

@@ -1222,6 +1222,37 @@ int bff_dbscan_link(const uint64_t *set, const uint64_t *core, const int32_t *pr
                     const int32_t *offs, const int32_t *order, int64_t n_voxels, int64_t n_source, const double *lo_host,
                     double cell, double eps, int32_t n_elems, int32_t *parent, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 3-D mask NMS over the rows of all query classes of a scene (assemble.py; the loop the
+ * reference left unreachable at tools/refinement_single.py:62-91, with a stable sort).
+ *
+ * K non-empty bit rows with a score each.  Rank: score descending, ties by ascending input index; order[r] = the input
+ * index of rank r (int32 [K], a permutation, made by the caller).  For ranks r < s with i = order[r], j = order[s],
+ * I = |row i & row j| and areas a:
+ *     BFF_NMS_IOU          v = (float)I / (float)(a_i + a_j - I)
+ *     BFF_NMS_CONTAINMENT  v = (float)I / (float)min(a_i, a_j)
+ * one float32 division of exactly converted integers (the caller guarantees 0 < a < 2^23), and r HITS s iff !(v < thres)
+ * in float32 -- the reference's keep-test `iou < nms_thres`, which torch evaluates in float32 -- and, with cls given,
+ * cls[i] == cls[j].  Greedy, in rank order: r is kept iff no kept q < r hits it.
+ *
+ * Limit: K <= 4096 (bff_resolve_overlaps_max_rows(); the Gram is K^2 int32), else BFF_E_LIMIT before anything is launched
+ * or written.  K == 0 returns 0 without a launch.  Neither entry point allocates or synchronises; neither uses atomics. */
+#define BFF_NMS_IOU 0
+#define BFF_NMS_CONTAINMENT 1
+
+/* inter: int32 [K][K] and area: int32 [K], both in INPUT order (bff_cross_popcount of the rows with themselves,
+ * bff_popcount_rows); cls: int32 [K] in input order or NULL; thres: not NaN; a criterion other than the two is BFF_E_ARG.
+ * sup: uint64 [K][ceil(K / 64)], written whole: bit s of row r is set iff r < s and r hits s; the bits with s <= r or
+ * s >= K are zero.  An entry of order outside [0, K) hits nothing and is hit by nothing. */
+int bff_nms_pairs(const int32_t *inter, const int32_t *area, const int32_t *order, const int32_t *cls, int32_t k,
+                  int32_t criterion, float thres, uint64_t *sup, void *stream);
+
+/* sup as bff_nms_pairs writes it (bits with s <= r zero).  keep_bits: uint64 [ceil(K / 64)], bit r = rank r is kept, the
+ * bits >= K zero; by: int32 [K] by rank, the smallest kept rank that hits r, -1 for a kept r; n_kept: int32 [1].  One
+ * wave walks the ranks (lane l holds word l of the removed set; the rows of sup are loaded ahead of the decisions), a
+ * second launch finds `by` for 64 ranks per wave. */
+int bff_nms_greedy(const uint64_t *sup, int32_t k, uint64_t *keep_bits, int32_t *by, int32_t *n_kept, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
