@@ -108,6 +108,8 @@ SIGNATURES = {
     "bff_dbscan_link": [_P, _P, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _L, _L, _P, _D, _D, _I, _P, _P],
     "bff_nms_pairs": [_P, _P, _P, _P, _I, _I, _F, _P, _P],
     "bff_nms_greedy": [_P, _I, _P, _P, _P, _P],
+    "bff_instance_views": [_P, _I, _L, _P, _P, _P, _I, _L, _L, _I, _I, _P, _P, _P],
+    "bff_select_views": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P],
 }
 PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, []), "bff_arch": (ctypes.c_char_p, []),
          "bff_masks2d_tile_pixels": (c_int32, []), "bff_label_runs_tile_pixels": (c_int32, []), "bff_mask_lookup_rows": (c_int32, [c_int32, c_int32, c_int64]),
@@ -121,7 +123,7 @@ PLAIN = {"bff_abi_version": (c_int32, []), "bff_last_error": (ctypes.c_char_p, [
          "bff_visibility_words": (c_int64, [c_int64]), "bff_visibility_builds": (c_int64, []),
          "bff_visibility_table_bytes": (c_int32, [c_int64, c_int32, c_int64, _P]),
          "bff_visibility_sorted_bytes": (c_int32, [c_int32, c_int32, c_int64, _P]),
-         "bff_sweep_runs_ok": (c_int32, [c_int64]),
+         "bff_sweep_runs_ok": (c_int32, [c_int64]), "bff_instance_views_lds_words": (c_int32, []),
          "bff_profile_next_sweep": (c_int32, [_P, _P]), "bff_event_create": (c_void_p, []),
          "bff_event_destroy": (c_int32, [_P]), "bff_event_elapsed_ms": (c_int32, [_P, _P, _P]),
          "bff_event_record": (c_int32, [_P, _P]), "bff_event_synchronize": (c_int32, [_P])}
@@ -432,6 +434,39 @@ def visibility_table(xyz_soa, n_points, slot_inv_pose, cam_intr, depth, height, 
     pix = torch.empty(max(n_pixels, 1), dtype=i32, device=dev)
     call("bff_visibility_table", *head, _ptr(pix, i32), n_pixels, _ptr(total, i64), 2)
     return (mask, off, pix, n_pixels) if with_count else (mask, off, pix)
+
+
+def instance_views_lds_words():
+    """Non-zero words of one instance bff_instance_views keeps in LDS; a fuller row is walked in global memory."""
+    return int(load().bff_instance_views_lds_words())
+
+
+def instance_views(rows, vis, n_pixels, height, width):
+    """rows: int64 [K][nw] instance bit rows in the sorted point order; vis = (vis_mask, vis_off, vis_pix) of visibility_table
+    with its n_pixels visible pairs.  -> (visible int32 [K][F], box int32 [K][F][4]) (bff_instance_views)."""
+    k, f = int(rows.shape[0]), int(vis[0].shape[0])
+    visible = torch.empty((k, f), dtype=i32, device=rows.device)
+    box = torch.empty((k, f, 4), dtype=i32, device=rows.device)
+    call("bff_instance_views", _ptr(rows, i64), k, rows.shape[1], _ptr(vis[0], i64), _ptr(vis[1], i32), _ptr(vis[2], i32), f,
+         vis[0].shape[1], int(n_pixels), height, width, _ptr(visible), _ptr(box))
+    return visible, box
+
+
+def select_views(visible, box, height, width, top_k, min_points, levels, expand):
+    """visible int32 [K][F], box int32 [K][F][4] -> (top int32 [K][top_k], top_visible int32 [K][top_k], crops int32
+    [K][top_k][levels][4]) (bff_select_views)."""
+    k, f = int(visible.shape[0]), int(visible.shape[1])
+    dev = visible.device
+    top = torch.empty((k, top_k), dtype=i32, device=dev)
+    top_visible = torch.empty((k, top_k), dtype=i32, device=dev)
+    crops = torch.empty((k, top_k, levels, 4), dtype=i32, device=dev)
+    if f == 0 and k:                                           # no slot, no launch: every entry is padding
+        top.fill_(-1)
+        top_visible.zero_()
+        crops.copy_(torch.tensor([width, height, -1, -1], dtype=i32, device=dev))
+    call("bff_select_views", _ptr(visible, i32), _ptr(box, i32), k, f, height, width, top_k, min_points, levels, float(expand),
+         _ptr(top), _ptr(top_visible), _ptr(crops))
+    return top, top_visible, crops
 
 
 def project_views_cached(n_points, depth_index, height, width, vis, mask_tab, mask_dir, run_start, run_end, view_mask_offs,

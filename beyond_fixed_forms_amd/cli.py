@@ -18,7 +18,8 @@ Beside the path: `reproject_main` renders a stage's instances back into the colo
 them into their spatially connected parts, `cluster_main` into their density clusters, `snap_main` snaps them to the
 scan's superpoints, `subsample_main` writes a voxel subsample of every cloud and `lift_main` carries the instances of a run
 on it back to the full cloud, and `assemble_main` gathers a scene's instances of all classes into one prediction, duplicates
-removed by a 3-D mask NMS (`evaluation_main --assembled` scores it); each writes to a directory of its own.  The four that turn a stage's files into files of
+removed by a 3-D mask NMS (`evaluation_main --assembled` scores it), and `select_views_main` finds the frames that see each
+instance best and the boxes to crop it with; each writes to a directory of its own.  The four that turn a stage's files into files of
 the same format (split, cluster, snap, lift) are one driver, `_stage_main`, with a per-scene function each.
 """
 from __future__ import annotations
@@ -668,6 +669,69 @@ def assemble_main(argv=None):
         got = assemble.assemble_scene(results, n_points, cfg, device)
         torch.save(assembled_dict(got, os.environ.get("BFF_SAVE_RLE") == "1", args.point_labels),
                    os.path.join(out_dir, f"{scene_id}.pth"))
+    return 0
+
+
+def _select_views_parser():
+    p = argparse.ArgumentParser(description="Beyond-Fixed-Forms: the frames that see each 3-D instance best, and the boxes to "
+                                            "crop it with (MI355X)")
+    p.add_argument("--config", type=str, required=True, help="Config")
+    p.add_argument("--cls", type=str, default=None, help="Class (not needed with --assembled)")
+    p.add_argument("--stage", type=str, default="final", choices=("final", "mask_3d"),
+                   help="Whose instances: the refinement's (final_output_dir) or the projection stage's (mask_3d_dir)")
+    p.add_argument("--every", type=int, default=None,
+                   help="Look at every n-th colour frame (default: downsample_ratio, the frames the 2-D stage saw)")
+    p.add_argument("--assembled", action="store_true",
+                   help="The scenes' assembled predictions (assembled_output_dir/<scene>.pth) instead of one class's files")
+    return p
+
+
+def select_views_main(argv=None):
+    """python tools/select_views_3d.py --config configs/config.yaml --cls "<class>" [--stage final|mask_3d] [--every n]
+                                        [--assembled]
+    For every scene of the class's output directory (with --assembled: of assembled_output_dir): per instance, the points
+    every n-th colour frame's depth confirms, their pixel box, the views_top_k best frames and their crops
+    (views.scene_views), saved to views_output_dir/<cls>/<scene>.pth (with --assembled: views_output_dir/<scene>.pth).
+    The depth frames are read, or rendered as depth_from_cloud / depth_from_mesh say."""
+    from . import views
+    from .io import load_scene_frames
+    from .scene import geometry_for_depth_frames
+    parser = _select_views_parser()
+    args = parser.parse_args(argv)
+    if not args.assembled and not args.cls:
+        parser.error("--cls is required without --assembled")
+    cfg = load_config(args.config)
+    cls = "" if args.assembled else args.cls
+    if args.assembled:
+        data_path = cfg.get("assembled_output_dir")
+        if not data_path:
+            raise ValueError("assembled_output_dir is not set in the config")
+    else:
+        data_path = os.path.join(cfg.final_output_dir if args.stage == "final" else cfg.mask_3d_dir, cls)
+    if not os.path.isdir(data_path):
+        what = "assembled output" if args.assembled else f"{args.stage} output for class {cls!r}"
+        print(f"no {what}: {data_path} is not a directory", file=sys.stderr)
+        return 1
+    out_dir = cfg.get("views_output_dir")
+    if not out_dir:
+        raise ValueError("views_output_dir is not set in the config")
+    views.check_config(cfg)                                      # a bad value stops the run before the first scene
+    every = int(cfg.downsample_ratio) if args.every is None else int(args.every)
+    if every < 1:
+        raise ValueError(f"--every must be >= 1, got {every}")
+    _lib.load()
+    _host_threads()
+    device = "cuda"
+    on_dev = os.environ.get("BFF_DEPTH_ON_DEVICE") == "1"
+    for name in sorted(s for s in os.listdir(data_path) if s.endswith(".pth")):
+        scene_id = name[:-4]
+        print("Working on", scene_id, "assembled" if args.assembled else f"class {cls}")
+        scene = load_scene_frames(cfg, scene_id, every, depth_on_device=on_dev)
+        geom = geometry_for_depth_frames(scene, cfg, list(scene.poses), device)
+        # the stage's own output file, written by this project's scripts or the reference's (a pickled dict of tensors)
+        result = torch.load(os.path.join(data_path, name), map_location="cpu", weights_only=False)
+        out = views.scene_views(geom, _saved_instances(result, geom.n_points, device), cfg)
+        save_result(out, out_dir, cls, scene_id)                 # cls "": views_output_dir/<scene>.pth
     return 0
 
 

@@ -75,6 +75,13 @@ DEFAULTS = dict(
     # <scene>.pth
     assemble_nms_thres=None, assemble_criterion="iou", assemble_scope="all", assemble_exclusive=False,
     assemble_min_points=1, assembled_output_dir=None,
+    # not keys of the reference either: the frames that see each 3-D instance best and the boxes to crop it with (views.py,
+    # tools/select_views_3d.py).  views_top_k: integer in 1 .. 64, the frames kept per instance, by the points the depth
+    # frame confirms; views_min_points: a frame that confirms fewer points is no candidate; views_crop_levels: integer in
+    # 1 .. 8, the crops per view, level l widened by l x floor(views_crop_expand x box side) pixels; views_crop_expand: a
+    # number >= 0.  5, 1, 3 and 0.1 are OpenMask3D's values, untuned here; views_output_dir: where the tool saves
+    # <cls>/<scene>.pth
+    views_top_k=5, views_min_points=1, views_crop_levels=3, views_crop_expand=0.1, views_output_dir=None,
 )
 
 

@@ -203,6 +203,29 @@ def load_scene(cfg, cls: str, scene_id: str, depth_on_device: bool = False, stag
                        mask_2d=mask_2d, color_files=color_files, height=h, width=w)
 
 
+def load_scene_frames(cfg, scene_id: str, every: int, depth_on_device: bool = False) -> SceneInputs:
+    """load_scene without a mask_2d file, for what reads a scene from its instances' side (tools/select_views_3d.py): the
+    cloud, the intrinsics and, of every `every`-th colour frame, the pose and the depth frame -- decoded as load_scene
+    decodes them, or left out where the config renders the depth.  `mask_2d` stays empty."""
+    from .scene import rendered_depth_stride, viewed_frame_ids
+    scene_dir = os.path.join(cfg.scene_2d_dir, scene_id)
+    cam_intr = read_matrix_txt(os.path.join(scene_dir, "intrinsic", "intrinsic_color.txt"))
+    points = np.load(os.path.join(cfg.scene_npy_dir, f"{scene_id}.npy"))
+    color_dir = os.path.join(scene_dir, "color")
+    color_files = [f for f in os.listdir(color_dir) if f.endswith(".jpg")] if os.path.isdir(color_dir) else []
+    need = viewed_frame_ids(color_files, every)
+    w, h = int(cfg.width_2d), int(cfg.height_2d)
+    fields = dict(points=points, cam_intr=cam_intr, mask_2d=[], color_files=color_files, height=h, width=w,
+                  poses={f: read_matrix_txt(os.path.join(scene_dir, "pose", f"{f}.txt")) for f in need})
+    if rendered_depth_stride(cfg):
+        return _scene_without_depth(cfg, scene_id, **fields)
+    paths = [os.path.join(scene_dir, "depth", f"{f}.png") for f in need]
+    if depth_on_device:
+        frames = decode_depth_pngs(paths)
+        return SceneInputs(scene_id=scene_id, depths={}, depths_raw={f: frames[i] for i, f in enumerate(need)}, **fields)
+    return SceneInputs(scene_id=scene_id, depths={f: load_depth(p, w, h) for f, p in zip(need, paths)}, **fields)
+
+
 def load_scene_classes(cfg, classes, scene_id: str, depth_on_device: bool = False, staging=None):
     """load_scene for several query classes of one scene: the cloud, the poses and the depth frames are read ONCE --
     every frame any class's mask list names, then the detection-ratio sweep's frames -- plus each class's

@@ -602,6 +602,14 @@ def _geometry(scene, cfg, ids, n_viewed, dev, sort_points, raw_depth_resident) -
     return new_geometry(scene, h, w, n, ids, inv, n_viewed, xyz, depth3, bounds, unsort, t32(perm))
 
 
+def geometry_for_depth_frames(scene, cfg, frame_ids, device="cuda") -> SceneGeometry:
+    """A SceneGeometry of the frames `frame_ids` ("1230" or "1230.jpg", one slot each in that order): the sorted cloud, the
+    inverse poses and the DEPTH frames -- the scene's own (scene.depths / depths_raw), or rendered as depth_from_cloud /
+    depth_from_mesh say -- and no viewed counts.  What reads a scene from its instances' side needs (views.scene_views)."""
+    ids = [str(f)[:-4] if str(f).endswith(".jpg") else str(f) for f in frame_ids]
+    return _geometry(scene, cfg, ids, 0, torch.device(device), True, None)
+
+
 def masks_all_rle(ft: FrameTable) -> bool:
     """Does every entry of the list hold its masks as RLE dicts (the mask_2d file's form)?"""
     return all(isinstance(e, (list, tuple)) for e in ft.mask_entries)

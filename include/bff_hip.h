@@ -1253,6 +1253,47 @@ int bff_nms_pairs(const int32_t *inter, const int32_t *area, const int32_t *orde
  * second launch finds `by` for 64 ranks per wave. */
 int bff_nms_greedy(const uint64_t *sup, int32_t k, uint64_t *keep_bits, int32_t *by, int32_t *n_kept, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The best views of 3-D instances and the boxes to crop them with, read off the visibility table (views.py; DESIGN.md
+ * section 7l; the reference has no such step).
+ *
+ * K instance bit rows in the SORTED point order (uint64 [K][nw], nw = ceil(n_points / 64), padding bits zero; rows may
+ * overlap and may be empty) against the table of F slots (vis_mask, vis_off, vis_pix as bff_visibility_table writes them,
+ * stride = bff_visibility_words(n_points) >= nw, n_pixels = the length of vis_pix).  S(k, f) = the points whose bit is
+ * set in row k and in vis_mask[f]:
+ *     visible int32 [K][F]      |S(k, f)|                               (= bff_cross_popcount of the rows and vis_mask)
+ *     box     int32 [K][F][4]   (min u, min v, max u, max v) over the pixels of S(k, f), inclusive; (width, height, -1, -1)
+ *                               where S is empty
+ * Top views: the candidates of k are the slots with visible >= max(1, min_points), ordered by visible descending, ties by
+ * ascending slot position:
+ *     top         int32 [K][top_k]             the t-th candidate's slot position, -1 past the candidates
+ *     top_visible int32 [K][top_k]             its count, 0 past the candidates
+ *     crops       int32 [K][top_k][levels][4]  for level l and the view's box (u0, v0, u1, v1):
+ *                     ex = (int)floor((double)(u1 - u0) * expand) * l,  ey = (int)floor((double)(v1 - v0) * expand) * l
+ *                     (max(0, u0 - ex), max(0, v0 - ey), min(width - 1, u1 + ex), min(height - 1, v1 + ey));
+ *                 (width, height, -1, -1) past the candidates.  One float64 product of exactly converted integers, the same
+ *                 on host and device (-ffp-contract=off); it is cut at 2^15 before the conversion -- beyond every image
+ *                 side, so the crop is the same and no expand overflows.
+ * Everything else is integer; there are no atomics; every element of every output is written exactly once (no pre-fill).
+ *
+ * Limits, checked before anything is launched: n_slots <= 65535; height, width < 2^15; K * F * 4 < 2^31; 1 <= top_k <= 64;
+ * 1 <= levels <= 8 -- else BFF_E_LIMIT; expand finite and >= 0, else BFF_E_ARG.  K == 0 or F == 0 returns 0 without a
+ * launch (nothing is written).  box and crops must be 16-byte aligned.  Neither entry point allocates or synchronises. */
+
+/* rows are read for w < nw only; vis_pix is never read at or beyond n_pixels (a pair there counts but moves no box).
+ * One workgroup per (instance, 16 slots): the row's non-zero words are compacted into LDS once (up to
+ * bff_instance_views_lds_words() of them; a fuller row is walked in global memory), one wave per slot walks them. */
+int bff_instance_views(const uint64_t *rows, int32_t n_rows, int64_t nw, const uint64_t *vis_mask, const uint32_t *vis_off,
+                       const uint32_t *vis_pix, int32_t n_slots, int64_t stride, int64_t n_pixels, int32_t height,
+                       int32_t width, int32_t *visible, int32_t *box, void *stream);
+int32_t bff_instance_views_lds_words(void);
+
+/* visible, box: as bff_instance_views writes them.  One wave per instance: top_k rounds of an arg-max over the slots on the
+ * key (count, -position), each below the key of the round before; the crops are written by the same kernel. */
+int bff_select_views(const int32_t *visible, const int32_t *box, int32_t n_rows, int32_t n_slots, int32_t height,
+                     int32_t width, int32_t top_k, int32_t min_points, int32_t levels, double expand, int32_t *top,
+                     int32_t *top_visible, int32_t *crops, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
